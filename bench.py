@@ -9,13 +9,21 @@ BASELINE.json configs[1] -- n=16, t=5, 2^20 secrets, 256-bit Fr -- per GPU (weak
 independent, there is no data-path collective).  Rank 0 prints ONE JSON line.
 
   value      shares/s (share evaluations), whole job (n * B * N * K / max-over-ranks time), inputs resident in HBM
+  ms_per_step  wall time of one timed step (max over ranks)
   roofline   dominant kernel against the HBM roofline: algorithmic bytes per launch (704 B/secret)
              / average launch duration measured with HIP events on the launch stream
-  cpu_baseline  the C restatement of the reference algorithm (oracle/, "port") timed on this box's
+
+A plain run does only that: set up, warm up, time the K steps, print the line.  --full adds everything else below (the
+recon half, the CPU baselines and the oracle check, the no-arithmetic traffic run, the extra rows; for --workload cfg4 /
+cfg5 the dominant kernel's own launches, the producers and the CPU baseline).  --dump-outputs DIR writes a fixed, seeded
+sample of what the last timed step computed (the per-party result shares) as DIR/<name>.npy, float64.
+
+  recon      (--full) recons/s of batch_recon on BASELINE configs[2], timed like `value`
+  cpu_baseline  (--full) the C restatement of the reference algorithm (oracle/, "port") timed on this box's
              host cores on a bounded sample of the same workload (single thread: the reference runs
              its arithmetic inline in one tokio task per party, no rayon).  This leg is the ONLY place
              the oracle is used; it also checks the first 512 secrets of the benchmarked buffers.
-  extra      cfg3 encode/decode rates, element-wise rate, the register-resident modmul ceiling
+  extra      (--full) cfg3 encode/decode rates, element-wise rate, the register-resident modmul ceiling
 """
 import argparse
 import gc
@@ -44,6 +52,28 @@ def shard_range(total: int, rank: int, world: int):
     base, rem = divmod(total, world)
     lo = rank * base + min(rank, rem)
     return lo, lo + base + (1 if rank < rem else 0)
+
+
+DUMP_COLUMNS = 1 << 14  # sampled columns per dumped array: 16 parties x 16384 x 8 words x 8 B = 16 MiB
+DUMP_SEED = 0xC0FFEE
+
+
+def dump_columns(out_dir, name, n, B, row):
+    """--dump-outputs: a [n][B] array of 256-bit field elements (four u64 limbs each), party p's row given by row(p) -> int64
+    tensor [B][4].  Writes a fixed, seeded sample of min(B, DUMP_COLUMNS) columns (the same for every run with the same B) as
+    out_dir/<name>.npy, float64 [n][S][8]: the eight little-endian u32 words of each element, each exact in float64; and the
+    sampled column indices as out_dir/<name>_columns.npy."""
+    import torch
+    S = min(B, DUMP_COLUMNS)
+    cols = np.sort(np.random.default_rng(DUMP_SEED).choice(B, S, replace=False))
+    words = np.empty((n, S, 8), dtype=np.float64)
+    for p in range(n):
+        r = row(p)
+        got = r[torch.as_tensor(cols, device=r.device)].cpu().numpy()  # [S][4] int64
+        words[p] = np.ascontiguousarray(got).view(np.uint32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"{name}.npy"), words)
+    np.save(os.path.join(out_dir, f"{name}_columns.npy"), cols.astype(np.float64))
 
 
 def timed_steps(step_fn, steps, warmup, sync_fn, barrier_fn, max_reduce_fn, prewarm_s=0.0, events=None, manage_gc=True):
@@ -350,6 +380,8 @@ def bench_single_process(args, torch):
         gc.enable()
     if errs:
         raise SystemExit(f"--single-process: {errs}")
+    if args.dump_outputs:  # device 0's shard: the same inputs as a one-GPU run
+        dump_columns(args.dump_outputs, "shares", n, B, lambda p: keep[0][0][p])
     secs = max(r[0]["secs"] for r in res)
     rsecs = max(r[1]["secs"] for r in res)
     kernel_ms = max(r[0]["kernel_ms"] for r in res)
@@ -427,7 +459,14 @@ def main():
     ap.add_argument("--with-producers", action="store_true",
                     help="--workload cfg4: time run_preprocessing's whole triple part -- RanSha (a, b), DouSha + RanDouSha ([r]_t, [r]_2t) "
                          "and the triple generation -- device-resident from the dealers' polynomials to [c]_t")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the recon half, the CPU baselines and "
+                         "the oracle check, the no-arithmetic traffic run and the extra rows (cfg4 / cfg5: the dominant kernel's "
+                         "own launches, the producers and the CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed, seeded sample of what the last step computed (the per-party "
+                         "result shares) to DIR/<name>.npy as float64")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave out the extra rows and the all-core CPU baseline")
     ap.add_argument("--no-final-gather", action="store_true",
                     help="N > 1: skip the all-gather of the shares after the timed region (the path's only collective)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -545,10 +584,13 @@ def bench_metric(ctx):
 
     step()
     torch.cuda.synchronize()
-    # the first secrets of the benchmarked buffers, for the oracle check inside the cpu_baseline leg
-    check = (coeffs[:512].cpu().numpy().view(np.uint64), shares[:, :512].cpu().numpy().view(np.uint64))
+    if args.full:
+        # the first secrets of the benchmarked buffers, for the oracle check inside the cpu_baseline leg
+        check = (coeffs[:512].cpu().numpy().view(np.uint64), shares[:, :512].cpu().numpy().view(np.uint64))
     tm = timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, ctx["barrier"], ctx["max_reduce"],
                      prewarm_s=args.prewarm_seconds, events=ctx["events"]())
+    if args.dump_outputs and rank == 0:
+        dump_columns(args.dump_outputs, "shares", n, B, lambda p: shares[p])
     secs, kernel_ms = tm["secs"], tm["kernel_ms"]
     value = n * B * world * args.steps / secs
     algo_bytes = (d + 1 + n) * 32 * B
@@ -574,23 +616,24 @@ def bench_metric(ctx):
     if rec:
         out["roofline"]["traffic"] = rec["hbm_bytes_per_launch"]
         out["roofline"]["traffic_source"] = rec["source"]
-    # context for `frac`, measured IN THIS RUN on the same buffers right behind the timed region (the chip is warm): the same
-    # loads and stores with no arithmetic at all (hbmpc_dev_traffic_ubench: x[B][d+1] -> y[n][B], every loaded word kept live)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(5):
-        assert eng.dev_traffic_ubench(coeffs.data_ptr(), B, d + 1, shares.data_ptr(), n, stream) == 0, eng.last_error()
-    e0.record()
-    for _ in range(20):
-        eng.dev_traffic_ubench(coeffs.data_ptr(), B, d + 1, shares.data_ptr(), n, stream)
-    e1.record()
-    torch.cuda.synchronize()
-    no_arith_ms = e0.elapsed_time(e1) / 20
-    out["roofline"]["same_traffic_no_arithmetic_ms"] = no_arith_ms
-    out["roofline"]["same_traffic_no_arithmetic_GBps"] = algo_bytes / (no_arith_ms * 1e-3) / 1e9
-    out["roofline"]["same_traffic_no_arithmetic_source"] = ("hbmpc_dev_traffic_ubench on the benchmarked buffers, 20 launches behind the "
-                                                            "timed region of this run (HIP events)")
-    step()  # the shares the checks below look at
-    torch.cuda.synchronize()
+    if args.full:
+        # context for `frac`, measured IN THIS RUN on the same buffers right behind the timed region (the chip is warm): the same
+        # loads and stores with no arithmetic at all (hbmpc_dev_traffic_ubench: x[B][d+1] -> y[n][B], every loaded word kept live)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(5):
+            assert eng.dev_traffic_ubench(coeffs.data_ptr(), B, d + 1, shares.data_ptr(), n, stream) == 0, eng.last_error()
+        e0.record()
+        for _ in range(20):
+            eng.dev_traffic_ubench(coeffs.data_ptr(), B, d + 1, shares.data_ptr(), n, stream)
+        e1.record()
+        torch.cuda.synchronize()
+        no_arith_ms = e0.elapsed_time(e1) / 20
+        out["roofline"]["same_traffic_no_arithmetic_ms"] = no_arith_ms
+        out["roofline"]["same_traffic_no_arithmetic_GBps"] = algo_bytes / (no_arith_ms * 1e-3) / 1e9
+        out["roofline"]["same_traffic_no_arithmetic_source"] = ("hbmpc_dev_traffic_ubench on the benchmarked buffers, 20 launches behind the "
+                                                                "timed region of this run (HIP events)")
+        step()  # the shares the checks below look at
+        torch.cuda.synchronize()
 
     final_gather = None
     if world > 1 and not args.no_final_gather:
@@ -609,6 +652,10 @@ def bench_metric(ctx):
                                       "(RCCL), read party-major through a permuted view: no copy after the collective"}
         del full
     del coeffs, shares
+    if final_gather:
+        out["final_gather"] = final_gather
+    if not args.full:
+        return out
 
     # ---- the recon half: batch_recover_secret on BASELINE configs[2], this rank's 2^20 chunks ----
     n3, t3, d3, G = 31, 10, 10, 1 << args.log2_batch
@@ -652,8 +699,6 @@ def bench_metric(ctx):
         out["recon"]["roofline"]["traffic_source"] = rec["source"]
     out["recons_per_s"] = out["recon"]["value"]
     out["roofline_recon"] = out["recon"]["roofline"]
-    if final_gather:
-        out["final_gather"] = final_gather
     del x, y, co, st
 
     if rank == 0 and world == 1:
@@ -731,6 +776,17 @@ def bench_pipeline(ctx):
     torch.cuda.synchronize()
     tm = timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, ctx["barrier"], ctx["max_reduce"],
                      prewarm_s=args.prewarm_seconds, events=ctx["events"]())
+    if args.dump_outputs and rank == 0:
+        # the result shares [n][N][4] (cfg4: [c]_t, cfg5: the fpmul outputs), party by party through one row-sized buffer
+        tmp = torch.empty((N, 4), dtype=torch.int64, device=dev)
+
+        def result_row(p):
+            eng.d2d(tmp.data_ptr(), result_ptr + p * N * 32, N * 32, stream)
+            torch.cuda.synchronize()
+            return tmp
+
+        dump_columns(args.dump_outputs, "c_shares" if args.workload == "cfg4" else "fpmul_out_shares", n, N, result_row)
+        del tmp
     out = {
         "metric": "shares/sec (compute_shares) + recons/sec (batch_recon), 256-bit Fr, 1/2/4/8 GPU",
         "value": total * args.steps / tm["secs"], "unit": unit, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -740,71 +796,72 @@ def bench_pipeline(ctx):
         "config": {"workload": what + f" (BASELINE configs[{3 if args.workload == 'cfg4' else 4}])", "field": "bls12-381 Fr",
                    "parallelism": f"batch-sharded x{world}, all {n} simulated parties of a shard on one GPU, no data-path collective"},
     }
-    # the dominant kernel of the step against the HBM roofline: its algorithmic bytes / its own launch duration, measured
-    # live with HIP events around K launches of that call alone (same buffers, same stream)
-    e0, e1, rec = ctx["events"]()
-    if args.workload == "cfg4":
-        d2 = 2 * t
-        G = N // m
-        dom = lambda: eng.dev_triple_encode_parties(tg.a, tg.b, tg.r2t, G, n, d2, n, tg.c, tg.Y, stream)
-        dom_bytes = n * (3 * N + n * G) * 32          # per party: a, b, r2t read, Y[party][n][G] written
-        dom_name = "k_mfma_bfly<11,8,8,TRIPLE,2>"     # the local products inside the matrix-core encode (kernels_mfma_bfly.hpp)
-        step_bytes = dom_bytes + (n * n * G + n * G) * 32 + (n * G + N) * 32 + n * N * 64 + N * 32
-        tkey = f"triple_encode_parties_n{n}_t{t}_N{N}"
-        limiter = ("HBM on a 67 % read / 33 % write stream of 32-byte elements at a 352-byte stride: the same launch with loads and stores only "
-                   "(every load kept live) takes 2.14 ms against 2.17 - 2.25 ms, profiles/r04_ablations_all_loads_live.txt")
-    else:
-        dom = lambda: eng.dev_fpmul_middle(fp.tc, fp.x, fp.y, fp.dop, fp.eop, fp.rbits, fp.rint, k, f, N, n, fp.z, fp.rdash, fp.osh, stream)
-        dom_bytes = n * N * 32 * (7 + f) + 2 * N * 32  # c, x, y, r_int, f bit shares read, z, r', open share written per party; d, e once
-        dom_name = "k_fpmul_middle<U29>"
-        # the first open reads a, b, x, y of its 2t + 1 senders and forms their shares itself (four launches: hbmpc_dev_fpmul_parties);
-        # the second reads the 2t + 1 senders' open shares; d, e, c out; TruncPr's last step z, r' in, the output shares out
-        step_bytes = dom_bytes + (2 * t + 1) * 4 * N * 32 + (2 * t + 1) * N * 32 + 3 * N * 32 + n * N * 32 * 3 + N * 32
-        tkey = f"fpmul_middle_n{n}_t{t}_N{N}_f{f}"
-        limiter = "HBM (element-wise, 5 - 6 TB/s: profiles/r04_cfg5_kernel_stats.csv)"
-    for _ in range(3):
-        dom()
-    torch.cuda.synchronize()
-    rec(e0)
-    for _ in range(args.steps):
-        dom()
-    rec(e1)
-    torch.cuda.synchronize()
-    dom_ms = e0.elapsed_time(e1) / args.steps
-    ach = dom_bytes / (dom_ms * 1e-3) / 1e9
-    out["roofline"] = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
-                       "kernel": dom_name, "kernel_ms": dom_ms, "algorithmic_bytes": dom_bytes, "limiter": limiter,
-                       "kernel_ms_source": "HIP events around K launches of this call alone, after the timed region",
-                       "step_algorithmic_bytes": step_bytes,
-                       "step_GBps": step_bytes / (tm["kernel_ms"] * 1e-3) / 1e9, "step_frac": step_bytes / (tm["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS}
-    trec = traffic_record(tkey)
-    if trec:
-        out["roofline"]["traffic"] = trec["hbm_bytes_per_launch"]
-        out["roofline"]["traffic_source"] = trec["source"]
-    if pre is not None:
-        # the producers alone (their share of the step), and their compulsory traffic
-        def ev_ms(fn):
-            a0, a1, r = ctx["events"]()
-            fn()
-            torch.cuda.synchronize()
-            r(a0)
-            for _ in range(args.steps):
+    if args.full:
+        # the dominant kernel of the step against the HBM roofline: its algorithmic bytes / its own launch duration, measured
+        # live with HIP events around K launches of that call alone (same buffers, same stream)
+        e0, e1, rec = ctx["events"]()
+        if args.workload == "cfg4":
+            d2 = 2 * t
+            G = N // m
+            dom = lambda: eng.dev_triple_encode_parties(tg.a, tg.b, tg.r2t, G, n, d2, n, tg.c, tg.Y, stream)
+            dom_bytes = n * (3 * N + n * G) * 32          # per party: a, b, r2t read, Y[party][n][G] written
+            dom_name = "k_mfma_bfly<11,8,8,TRIPLE,2>"     # the local products inside the matrix-core encode (kernels_mfma_bfly.hpp)
+            step_bytes = dom_bytes + (n * n * G + n * G) * 32 + (n * G + N) * 32 + n * N * 64 + N * 32
+            tkey = f"triple_encode_parties_n{n}_t{t}_N{N}"
+            limiter = ("HBM on a 67 % read / 33 % write stream of 32-byte elements at a 352-byte stride: the same launch with loads and stores only "
+                       "(every load kept live) takes 2.14 ms against 2.17 - 2.25 ms, profiles/r04_ablations_all_loads_live.txt")
+        else:
+            dom = lambda: eng.dev_fpmul_middle(fp.tc, fp.x, fp.y, fp.dop, fp.eop, fp.rbits, fp.rint, k, f, N, n, fp.z, fp.rdash, fp.osh, stream)
+            dom_bytes = n * N * 32 * (7 + f) + 2 * N * 32  # c, x, y, r_int, f bit shares read, z, r', open share written per party; d, e once
+            dom_name = "k_fpmul_middle<U29>"
+            # the first open reads a, b, x, y of its 2t + 1 senders and forms their shares itself (four launches: hbmpc_dev_fpmul_parties);
+            # the second reads the 2t + 1 senders' open shares; d, e, c out; TruncPr's last step z, r' in, the output shares out
+            step_bytes = dom_bytes + (2 * t + 1) * 4 * N * 32 + (2 * t + 1) * N * 32 + 3 * N * 32 + n * N * 32 * 3 + N * 32
+            tkey = f"fpmul_middle_n{n}_t{t}_N{N}_f{f}"
+            limiter = "HBM (element-wise, 5 - 6 TB/s: profiles/r04_cfg5_kernel_stats.csv)"
+        for _ in range(3):
+            dom()
+        torch.cuda.synchronize()
+        rec(e0)
+        for _ in range(args.steps):
+            dom()
+        rec(e1)
+        torch.cuda.synchronize()
+        dom_ms = e0.elapsed_time(e1) / args.steps
+        ach = dom_bytes / (dom_ms * 1e-3) / 1e9
+        out["roofline"] = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
+                           "kernel": dom_name, "kernel_ms": dom_ms, "algorithmic_bytes": dom_bytes, "limiter": limiter,
+                           "kernel_ms_source": "HIP events around K launches of this call alone, after the timed region",
+                           "step_algorithmic_bytes": step_bytes,
+                           "step_GBps": step_bytes / (tm["kernel_ms"] * 1e-3) / 1e9, "step_frac": step_bytes / (tm["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS}
+        trec = traffic_record(tkey)
+        if trec:
+            out["roofline"]["traffic"] = trec["hbm_bytes_per_launch"]
+            out["roofline"]["traffic_source"] = trec["source"]
+        if pre is not None:
+            # the producers alone (their share of the step), and their compulsory traffic
+            def ev_ms(fn):
+                a0, a1, r = ctx["events"]()
                 fn()
-            r(a1)
-            torch.cuda.synchronize()
-            return a0.elapsed_time(a1) / args.steps
-        Krs, Krd = pre.K_rs, pre.K_rd
-        # deal: coefficients in, n^2 K shares out; mix: n^2 K in (the dealt rows, read in place), n^2 K out; verifiers: their
-        # sender rows in, polynomials out; output slices in and out
-        rs_b = (n * Krs * (t + 1) + 3 * n * n * Krs + 2 * t * ((2 * t + 1) * Krs + Krs * (t + 1)) + 2 * n * (n - 2 * t) * Krs) * 32
-        rd_b = (n * Krd * (3 * t + 2) + 6 * n * n * Krd + (n - t - 1) * 4 * n * Krd + 4 * n * (t + 1) * Krd) * 32
-        rs_ms, rd_ms = ev_ms(lambda: pre.rs.run(check=False)), ev_ms(lambda: pre.rd.run(check=False))
-        out["producers"] = {"ransha_ms": rs_ms, "ransha_algorithmic_bytes": rs_b, "ransha_GBps": rs_b / rs_ms / 1e6,
-                            "randousha_ms": rd_ms, "randousha_algorithmic_bytes": rd_b, "randousha_GBps": rd_b / rd_ms / 1e6,
-                            "batch_elements_per_dealer": {"ransha": Krs, "randousha": Krd}}
-        out["roofline"]["step_algorithmic_bytes"] = step_bytes + rs_b + rd_b
-        out["roofline"]["step_GBps"] = (step_bytes + rs_b + rd_b) / (tm["kernel_ms"] * 1e-3) / 1e9
-        out["roofline"]["step_frac"] = out["roofline"]["step_GBps"] / HBM_PEAK_GBS
+                torch.cuda.synchronize()
+                r(a0)
+                for _ in range(args.steps):
+                    fn()
+                r(a1)
+                torch.cuda.synchronize()
+                return a0.elapsed_time(a1) / args.steps
+            Krs, Krd = pre.K_rs, pre.K_rd
+            # deal: coefficients in, n^2 K shares out; mix: n^2 K in (the dealt rows, read in place), n^2 K out; verifiers: their
+            # sender rows in, polynomials out; output slices in and out
+            rs_b = (n * Krs * (t + 1) + 3 * n * n * Krs + 2 * t * ((2 * t + 1) * Krs + Krs * (t + 1)) + 2 * n * (n - 2 * t) * Krs) * 32
+            rd_b = (n * Krd * (3 * t + 2) + 6 * n * n * Krd + (n - t - 1) * 4 * n * Krd + 4 * n * (t + 1) * Krd) * 32
+            rs_ms, rd_ms = ev_ms(lambda: pre.rs.run(check=False)), ev_ms(lambda: pre.rd.run(check=False))
+            out["producers"] = {"ransha_ms": rs_ms, "ransha_algorithmic_bytes": rs_b, "ransha_GBps": rs_b / rs_ms / 1e6,
+                                "randousha_ms": rd_ms, "randousha_algorithmic_bytes": rd_b, "randousha_GBps": rd_b / rd_ms / 1e6,
+                                "batch_elements_per_dealer": {"ransha": Krs, "randousha": Krd}}
+            out["roofline"]["step_algorithmic_bytes"] = step_bytes + rs_b + rd_b
+            out["roofline"]["step_GBps"] = (step_bytes + rs_b + rd_b) / (tm["kernel_ms"] * 1e-3) / 1e9
+            out["roofline"]["step_frac"] = out["roofline"]["step_GBps"] / HBM_PEAK_GBS
     if world > 1 and not args.no_final_gather:
         from mpc_protocols_amd import sharding
         # this rank's result shares as a torch view of the pipeline's device buffer: [n][N][4]
@@ -824,7 +881,7 @@ def bench_pipeline(ctx):
                                "collective": "all_gather of the [n][N_rank] result shares (RCCL)"}
         del full, mine
     pipe.close()
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline_pipeline(args.workload, n, t)
     return out
 

@@ -20,6 +20,14 @@ def _env():
     return env
 
 
+def _env_without_gpu():
+    """the same, with every device hidden from the child processes: the tests below follow the paths that find no GPU,
+    on a machine that has one as well"""
+    env = _env()
+    env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = "-1"
+    return env
+
+
 def test_child_command_line():
     out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "cfg4", "--print-launch"],
                          capture_output=True, text=True, env=_env(), timeout=120)
@@ -36,7 +44,8 @@ def test_child_command_line():
 
 def test_one_gpu_needs_no_launcher():
     # N = 1 (the default) must not spawn anything: without a GPU it ends in bench.py's own message
-    out = subprocess.run([sys.executable, BENCH, "--steps", "1", "--warmup", "0"], capture_output=True, text=True, env=_env(), timeout=300)
+    out = subprocess.run([sys.executable, BENCH, "--steps", "1", "--warmup", "0"], capture_output=True, text=True, env=_env_without_gpu(),
+                         timeout=300)
     assert out.returncode != 0 and "needs an MI355X" in out.stderr and "torch.distributed" not in out.stderr
 
 
@@ -44,7 +53,7 @@ def test_spawns_the_ranks_and_returns_their_exit_code():
     # a real spawn: the ranks start, find no GPU and exit non-zero (the launcher stops the others as soon as one has failed,
     # so one message is guaranteed, not two); the parent relays their stderr and their exit code
     out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "1", "--warmup", "0"], capture_output=True, text=True,
-                         env=_env(), timeout=600)
+                         env=_env_without_gpu(), timeout=600)
     assert out.returncode != 0
     assert out.stderr.count("needs an MI355X") >= 1, out.stderr[-2000:]
     assert out.stdout.strip() == ""  # no bench record
