@@ -233,10 +233,7 @@ bool try_mfma_recover(hbmpc_ctx* ctx, const SortedSenders& ss, const RecoverArgs
         a.sub_half = pair->N, a.row_stride = pair->N;
         return launch_mfma_rows_sub(mi, a, ctx->device, s);
     }
-    if (!(launch_mfma_rows_a(mi, a, ctx->device, s, team) || launch_mfma_rows_b(mi, a, ctx->device, s, team) ||
-          launch_mfma_rows_c(mi, a, ctx->device, s, team) || launch_mfma_rows_d(mi, a, ctx->device, s, team)))
-        return false;
-    return true;
+    return launch_mfma_rows(mi, a, ctx->device, s, team);
 }
 
 // The same over Goldilocks (kernels_mfma_gl.hpp): the table is a few KB and costs microseconds to build, every row of a call
@@ -514,8 +511,7 @@ ShareErrorCode batch_recover_dev(hbmpc_ctx* ctx, const size_t* sender_ids, size_
     } else if (second_coeff >= 0) {
         return HBMPC_NOT_FUSED;  // no other kernel family writes two selected coefficients (nothing was enqueued)
     } else if (impl == IMPL_U29 && m <= 16 && !ctx->force_generic)
-        hit = launch_recover_a((int)m, p0, ra, grid, s) || launch_recover_b((int)m, p0, ra, grid, s) ||
-              launch_recover_c((int)m, p0, ra, grid, s) || launch_recover_d((int)m, p0, ra, grid, s);
+        hit = launch_recover((int)m, p0, ra, grid, s);
     else if (impl == IMPL_GOLD && m <= 16 && !ctx->force_generic)
         hit = launch_gold_recover((int)m, p0, ra, grid, s);
     if (!hit) launch_recover_generic(impl, p0, ra, grid, s);
@@ -763,17 +759,13 @@ static ShareErrorCode batch_interpolate_dev(hbmpc_ctx* ctx, const size_t* ids, s
                 if (c0_out_dev && degree_out_dev && ctx->list_rows_in_kernel)  // only coefficient 0 is stored (DEG instances: n = 8, 16)
                     a.out = (uint8_t*)c0_out_dev, a.out_stride = 1, a.store_rows = 1;
                 const int mi = (int)n;
-                auto go = [&] {
-                    return launch_mfma_bfly_a(mi, a, ctx->device, s) || launch_mfma_bfly_b(mi, a, ctx->device, s) ||
-                           launch_mfma_bfly_c(mi, a, ctx->device, s) || launch_mfma_bfly_d(mi, a, ctx->device, s);
-                };
                 a.ncoeffs = degree_out_dev;  // the kernel writes the degrees itself where an instance for it exists (n = 8, 16)
-                done = go();
+                done = launch_mfma_bfly(mi, a, ctx->device, s);
                 if (done && degree_out_dev) degree_in_kernel = true;
                 if (!done && degree_out_dev) {
                     a.ncoeffs = nullptr;
                     a.out = (uint8_t*)coeffs_out_dev, a.out_stride = n, a.store_rows = 0;
-                    done = go();
+                    done = launch_mfma_bfly(mi, a, ctx->device, s);
                 }
                 if (done && degree_in_kernel && a.store_rows == 1) {
                     HIP_TRY(ctx, hipGetLastError());

@@ -26,6 +26,7 @@
 #include "tables_mfma_gl.hpp"
 #include "kernels_mfma.hpp"
 #include "kernels_mfma_gl.hpp"
+#include "encode_route.hpp"
 
 using namespace hbmpc;
 
@@ -663,149 +664,106 @@ extern "C" void hbmpc_graph_destroy(hbmpc_graph* graph) {
 }
 
 // ---- a3 / a5: evaluation on the domain ---------------------------------------------------------
-// apply_vandermonde / compute_shares as int8 MFMA tiles (kernels_mfma.hpp): row j of the table is (alpha_j^k)_k
-// x_row_stride != 0: x is given as d + 1 ROWS of G elements, x_row_stride elements apart (the point-pair kernel only)
-// lists (the producers' mixing step, MfmaRowsArgs::list): only the point-pair kernel writes them; with lists set the call
-// returns false unless that kernel ran
+// Which kernel an encode takes is decided in one place, plan_encode (encode_route.hpp); the functions below build the tables,
+// fill the kernel arguments and walk its candidates.
+// the producers' lists of a rows call (hbmpc_dev_vandermonde_apply_rows_lists / _split, MfmaRowsArgs::list)
 struct ListSpec {
     size_t row0, rows, K;
     const hbmpc_list_slice* slices;
     size_t n_slices;
     void* others = nullptr;  // non-null: the rows outside the lists go here, party-major: others[(j (n - rows) + r') K + k] (hbmpc_dev_vandermonde_apply_rows_split)
 };
-// x[P][G][M] -> y[P][n][G] as ONE launch of the point-pair kernel over the P G chunks (k_mfma_bfly<.., LISTS> with every row party-major,
-// tu_mfma_bfly.inc: launch_lists): domains of 8 and 16 points, M <= 11, dense output rows, enough tiles over all parties to fill the chip
-static bool party_batched_one_launch(const hbmpc_ctx* ctx, size_t G, size_t n, size_t dp1, const EvalOut& y) {
-    const size_t size = domain_size(n);
-    return y.parties > 1 && y.ys == 0 && ctx->impl == IMPL_U29 && ctx->matrix_cores && ctx->mfma_bfly && !ctx->force_generic && size >= 8 && size <= 16 &&
-           n > size / 2 && dp1 >= 2 && dp1 <= 11 && ((size_t)y.parties * G + 31) / 32 > (size_t)(ctx->mfma_wgs ? ctx->mfma_wgs : ctx->n_cus) * 2 &&
-           (size_t)y.parties * n * G * 32 < ((size_t)1 << 32) && (size_t)y.parties * G * dp1 * 32 < ((size_t)1 << 32);
+static EncodeKnobs encode_knobs(const hbmpc_ctx* ctx) {
+    return EncodeKnobs{ctx->impl, ctx->force_generic, ctx->matrix_cores, ctx->mfma_team, ctx->mfma_bfly, ctx->list_rows_in_kernel,
+                       ctx->wide_max_chunks, ctx->mfma_min_encode, ctx->mfma_min_gold, ctx->mfma_wgs, ctx->n_cus};
 }
-static bool try_mfma_eval(hbmpc_ctx* ctx, const uint32_t* x, size_t G, size_t n, size_t dp1, EvalOut y, hipStream_t s,
-                          ShareErrorCode* rc_out, size_t x_row_stride = 0, const ListSpec* lists = nullptr) {
+// rows alpha_j^k (j < n, k < dp1) of the encode's matrix-core tables, times `scale`
+template <class H>
+static std::vector<std::vector<H>> vandermonde(size_t n, size_t dp1, H scale = H::one()) {
+    std::vector<H> el = domain_elements<H>(n, n);
+    std::vector<std::vector<H>> V(n, std::vector<H>(dp1));
+    for (size_t j = 0; j < n; ++j) {
+        H p = scale;
+        for (size_t k = 0; k < dp1; ++k) V[j][k] = p, p = p * el[j];
+    }
+    return V;
+}
+// the matrix-core routes of plan_mfma (encode_route.hpp) as int8 MFMA tiles (kernels_mfma.hpp, kernels_mfma_bfly.hpp).  Returns false
+// when the route does not run (its launcher declines, or the point-pair table's digit-sum bound does not hold: tables_mfma.hpp) and
+// nothing was enqueued; true when it ran or *rc_out holds an error.
+// x_row_stride != 0: x is given as d + 1 ROWS of G elements, x_row_stride elements apart (the point-pair kernel only)
+static bool run_mfma(hbmpc_ctx* ctx, const EncodeRoute& r, const uint32_t* x, size_t G, size_t n, size_t dp1, EvalOut y, hipStream_t s,
+                     ShareErrorCode* rc_out, size_t x_row_stride = 0, const ListSpec* lists = nullptr) {
     *rc_out = ShareSuccess;
-    const size_t rowb = mf_row_bytes(dp1);
     mf::MfmaRowsArgs a;
     memset(&a, 0, sizeof a);
-    // up to two tiles per workgroup: the workgroup-per-tile kernel (kernels_mfma_team.hpp; no verify rows here, so no barriers)
-    const int nwg = ctx->mfma_wgs ? ctx->mfma_wgs : ctx->n_cus;
-    // (measured, 4 096 .. 16 384 chunks: n = 20, d = 6: 6.7 .. 10.0 us against 19 .. 20; n = 31, d = 10 -- three roles --
-    // 9.8 and 15.1 us against 17.6 and 18.2 at 4 096 and 8 192 chunks, behind at 16 384)
-    // several parties' encodes in one launch (below): the tiles of all of them count
-    const bool parties_one = party_batched_one_launch(ctx, G, n, dp1, y) && !lists && !x_row_stride;
-    bool team = ctx->mfma_team && x_row_stride == 0 && dp1 <= MF_MAX_M && (G + 31) / 32 <= (size_t)nwg * 2 && !parties_one;
-    bool plain_ok = x_row_stride == 0 && dp1 <= MF_MAX_M && mf::mf_plan_roles((int)n, 0, (int)((160 * 1024 - (team ? 128 : 0)) / rowb), nwg, &a);
-    if (plain_ok && team && a.nroles > 1 && (G + 31) / 32 > (size_t)nwg) {
-        team = false;
-        plain_ok = mf::mf_plan_roles((int)n, 0, (int)((160 * 1024) / rowb), nwg, &a);
-    }
-    if (!plain_ok) team = false;  // the point pairs below may still fit (half the rows)
-    auto vandermonde = [&] {
-        std::vector<HFr> el = domain_elements<HFr>(n, n);
-        std::vector<std::vector<HFr>> V(n, std::vector<HFr>(dp1));
-        for (size_t j = 0; j < n; ++j) {
-            HFr p = HFr::one();
-            for (size_t k = 0; k < dp1; ++k) {
-                V[j][k] = p;
-                p = p * el[j];
-            }
-        }
-        return V;
-    };
+    mf::mf_take_plan(r.plan, &a);
     a.G = G;
     a.in_chunk_major = 1;
     a.nv = 0;
     a.out_party_major = 1;
     a.out_stride = y.ys ? y.ys : G;
     const int mi = (int)dp1;
-    // Large batches take the points in pairs (k, k + size / 2): alpha_{k + size/2} = -alpha_k, so both outputs come from
-    // the same M MFMAs (kernels_mfma_bfly.hpp) -- config 2: 0.16 ms against 0.18, config 3's encode 0.32 against 0.50
-    // (profiles/r03_mfma_bfly_ubench.txt).  The workgroup-per-tile kernel keeps the plain rows.
+    const uint32_t* tab;
+    if (r.kernel == EncodeKernel::MfmaRows || r.kernel == EncodeKernel::MfmaRowsTeam) {
+        *rc_out = get_table(ctx, key("mfvand", {n, dp1}, ctx->impl), [&] { return build_mfma_table(vandermonde<HFr>(n, dp1), dp1); }, &tab);
+        if (*rc_out != ShareSuccess) return true;
+        a.table = (const uint8_t*)tab;
+        // party-batched calls (x[P][G][d+1] -> y[P][n][G]): one launch per party (each is >= tens of microseconds)
+        for (unsigned p = 0; p < y.parties; ++p) {
+            a.in = (const uint8_t*)x + (size_t)p * G * dp1 * 32;
+            a.out = (uint8_t*)y.y + (size_t)p * n * a.out_stride * 32;
+            if (!launch_mfma_rows(mi, a, ctx->device, s, r.kernel == EncodeKernel::MfmaRowsTeam)) return false;
+        }
+        return true;
+    }
     const size_t half = domain_size(n) / 2;
-    if (!team && ctx->mfma_bfly && half >= 2 && n > half) {
-        mf::MfmaRowsArgs b = a;
-        if (mf::mf_plan_pairs((int)half, (int)((160 * 1024) / mf_bfly_row_bytes(dp1)), nwg, &b)) {
-            const uint32_t* tab;
-            std::array<size_t, 5> aux = {0, 0, 0, 0, 0};  // aux[0]: the table's words (0: its digit-sum bound does not hold, tables_mfma.hpp)
-            *rc_out = get_table(ctx, key("mfbfly", {n, dp1}, ctx->impl), [&] {
-                std::vector<uint32_t> tbl = build_mfma_bfly_table(vandermonde(), dp1, half);
-                aux[0] = tbl.size();
-                return tbl;
-            }, &tab, &aux);
-            if (*rc_out != ShareSuccess) return true;
-            bool ok = aux[0] != 0;
-            b.table = (const uint8_t*)tab;
-            b.half = (int)half, b.nout = (int)n;
-            if (x_row_stride) {
-                b.in_chunk_major = 0, b.row_stride = x_row_stride;
-                for (size_t i = 0; i < dp1; ++i) b.rows.set(i, (unsigned)i);
-            }
-            if (lists) {
-                b.list_row0 = (int)lists->row0, b.list_rows = (int)lists->rows, b.list_K = (uint32_t)lists->K;
-                if (lists->others) b.other_stride = (uint32_t)((n - lists->rows) * lists->K);
-                for (size_t k = 0; k < 2; ++k) {
-                    const bool have = k < lists->n_slices;
-                    b.list[k].dst = have ? (uint8_t*)lists->slices[k].dst_dev : nullptr;
-                    b.list[k].stride = have ? lists->slices[k].party_stride : 0;
-                    b.list[k].k0 = have ? (uint32_t)lists->slices[k].k0 : 0u;
-                    b.list[k].count = have ? (uint32_t)lists->slices[k].count : 0u;
-                }
-            }
-            // party-batched calls x[P][G][M] -> y[P][n][G]: ONE launch over the P G chunks where the instance with party-major "other" rows
-            // covers the shape (MfmaRowsArgs::other_stride with no list rows: chunk (p, g) of row k goes to ((p n + k) G + g)) -- the
-            // dealers' encodes of the producers; otherwise a launch per party
-            if (parties_one && b.nroles == 1 && (b.role[0].nrows == 4 || b.role[0].nrows == 8)) {
-                mf::MfmaRowsArgs pb = b;  // the plan does not depend on the number of chunks (workgroups stride over the tiles)
-                pb.G = (size_t)y.parties * G, pb.list_K = (uint32_t)G, pb.other_stride = (uint32_t)(n * G), pb.list_row0 = 0, pb.list_rows = 0;
-                pb.in = (const uint8_t*)x, pb.out = (uint8_t*)y.y;
-                if (launch_mfma_bfly_a(mi, pb, ctx->device, s) || launch_mfma_bfly_b(mi, pb, ctx->device, s) || launch_mfma_bfly_c(mi, pb, ctx->device, s) ||
-                    launch_mfma_bfly_d(mi, pb, ctx->device, s))
-                    return true;
-            }
-            for (unsigned p = 0; p < y.parties && ok; ++p) {  // party-batched calls: one launch per party
-                b.in = (const uint8_t*)x + (size_t)p * G * dp1 * 32;
-                b.out = lists && lists->others ? (uint8_t*)lists->others : (uint8_t*)y.y + (size_t)p * n * b.out_stride * 32;
-                ok = launch_mfma_bfly_a(mi, b, ctx->device, s) || launch_mfma_bfly_b(mi, b, ctx->device, s) ||
-                     launch_mfma_bfly_c(mi, b, ctx->device, s) || launch_mfma_bfly_d(mi, b, ctx->device, s);
-                if (!ok && p > 0) return false;  // cannot happen: the first party's launch decides
-            }
-            if (ok) return true;
+    std::array<size_t, 5> aux = {0, 0, 0, 0, 0};  // aux[0]: the table's words (0: its digit-sum bound does not hold, tables_mfma.hpp)
+    *rc_out = get_table(ctx, key("mfbfly", {n, dp1}, ctx->impl), [&] {
+        std::vector<uint32_t> tbl = build_mfma_bfly_table(vandermonde<HFr>(n, dp1), dp1, half);
+        aux[0] = tbl.size();
+        return tbl;
+    }, &tab, &aux);
+    if (*rc_out != ShareSuccess) return true;
+    if (aux[0] == 0) return false;
+    a.table = (const uint8_t*)tab;
+    a.half = (int)half, a.nout = (int)n;
+    if (x_row_stride) {
+        a.in_chunk_major = 0, a.row_stride = x_row_stride;
+        for (size_t i = 0; i < dp1; ++i) a.rows.set(i, (unsigned)i);
+    }
+    if (lists) {
+        a.list_row0 = (int)lists->row0, a.list_rows = (int)lists->rows, a.list_K = (uint32_t)lists->K;
+        if (lists->others) a.other_stride = (uint32_t)((n - lists->rows) * lists->K);
+        for (size_t k = 0; k < 2; ++k) {
+            const bool have = k < lists->n_slices;
+            a.list[k].dst = have ? (uint8_t*)lists->slices[k].dst_dev : nullptr;
+            a.list[k].stride = have ? lists->slices[k].party_stride : 0;
+            a.list[k].k0 = have ? (uint32_t)lists->slices[k].k0 : 0u;
+            a.list[k].count = have ? (uint32_t)lists->slices[k].count : 0u;
         }
     }
-    if (!plain_ok || lists) return false;
-    const uint32_t* tab;
-    *rc_out = get_table(ctx, key("mfvand", {n, dp1}, ctx->impl), [&] { return build_mfma_table(vandermonde(), dp1); }, &tab);
-    if (*rc_out != ShareSuccess) return true;
-    a.table = (const uint8_t*)tab;
-    // party-batched calls (x[P][G][d+1] -> y[P][n][G]): one launch per party (each is >= tens of microseconds)
+    // party-batched calls x[P][G][M] -> y[P][n][G]: ONE launch over the P G chunks where the instance with party-major "other" rows
+    // covers the shape (MfmaRowsArgs::other_stride with no list rows: chunk (p, g) of row k goes to ((p n + k) G + g)) -- the
+    // dealers' encodes of the producers; otherwise a launch per party
+    if (r.kernel == EncodeKernel::BflyParties) {
+        a.G = (size_t)y.parties * G, a.list_K = (uint32_t)G, a.other_stride = (uint32_t)(n * G), a.list_row0 = 0, a.list_rows = 0;
+        a.in = (const uint8_t*)x, a.out = (uint8_t*)y.y;
+        return launch_mfma_bfly(mi, a, ctx->device, s);  // the plan does not depend on the number of chunks (workgroups stride over the tiles)
+    }
     for (unsigned p = 0; p < y.parties; ++p) {
         a.in = (const uint8_t*)x + (size_t)p * G * dp1 * 32;
-        a.out = (uint8_t*)y.y + (size_t)p * n * a.out_stride * 32;
-        if (!(launch_mfma_rows_a(mi, a, ctx->device, s, team) || launch_mfma_rows_b(mi, a, ctx->device, s, team) ||
-              launch_mfma_rows_c(mi, a, ctx->device, s, team) || launch_mfma_rows_d(mi, a, ctx->device, s, team)))
-            return false;
+        a.out = lists && lists->others ? (uint8_t*)lists->others : (uint8_t*)y.y + (size_t)p * n * a.out_stride * 32;
+        if (!launch_mfma_bfly(mi, a, ctx->device, s)) return false;  // only the first party's launch can decline: the shape decides
     }
     return true;
 }
 
 // the same over Goldilocks (kernels_mfma_gl.hpp): all n rows in every workgroup's LDS
-static bool try_mfma_eval_gl(hbmpc_ctx* ctx, const uint32_t* x, size_t G, size_t n, size_t dp1, EvalOut y, hipStream_t s,
-                             ShareErrorCode* rc_out) {
+static bool run_mfma_gl(hbmpc_ctx* ctx, const uint32_t* x, size_t G, size_t n, size_t dp1, EvalOut y, hipStream_t s, ShareErrorCode* rc_out) {
     *rc_out = ShareSuccess;
-    if (mfgl_table_bytes(n, dp1) + 2048 > 160 * 1024) return false;
     const uint32_t* tab;
-    *rc_out = get_table(ctx, key("mfvandgl", {n, dp1}, ctx->impl), [&] {
-        std::vector<HGl> el = domain_elements<HGl>(n, n);
-        std::vector<std::vector<HGl>> V(n, std::vector<HGl>(dp1));
-        for (size_t j = 0; j < n; ++j) {
-            HGl p = HGl::one();
-            for (size_t k = 0; k < dp1; ++k) {
-                V[j][k] = p;
-                p = p * el[j];
-            }
-        }
-        return build_mfma_table_gl(V, dp1);
-    }, &tab);
+    *rc_out = get_table(ctx, key("mfvandgl", {n, dp1}, ctx->impl), [&] { return build_mfma_table_gl(vandermonde<HGl>(n, dp1), dp1); }, &tab);
     if (*rc_out != ShareSuccess) return true;
     mf::MfmaGlArgs a;
     memset(&a, 0, sizeof a);
@@ -841,88 +799,70 @@ static ShareErrorCode vmat_table(hbmpc_ctx* ctx, size_t n, size_t d, const uint3
         return w;
     }, out);
 }
+// the chunk-major encode: the candidates of plan_encode in order, the first that runs does the call
 static ShareErrorCode eval_impl(hbmpc_ctx* ctx, const uint32_t* x, size_t G, size_t n, size_t d, EvalOut y,
                                 hipStream_t s) {
     const size_t size = domain_size(n), dp1 = d + 1;
-    ShareErrorCode rc_mf = ShareSuccess;
     const int impl = ctx->impl;
     const bool gold = impl == IMPL_GOLD;
-    if (G * y.parties <= ctx->wide_max_chunks / 4 && !ctx->force_generic) {  // small batch: wave per chunk
-        if (impl == IMPL_U29 && n * dp1 * 36 <= 48 * 1024) {  // as a table product, the lanes sharing a point's terms (k_eval_wide_dot)
+    const EncodePlan plan = plan_encode(encode_knobs(ctx), EncodeShape{EncodeKind::ChunkMajor, G, n, d, y.parties, y.ys});
+    for (int i = 0; i < plan.count; ++i) {
+        const EncodeRoute& r = plan.route[i];
+        ShareErrorCode rc = ShareSuccess;
+        switch (r.kernel) {
+        case EncodeKernel::WideDot: {
             const uint32_t* vmat;
-            ShareErrorCode rc = vmat_table(ctx, n, d, &vmat);
+            rc = vmat_table(ctx, n, d, &vmat);
             if (rc != ShareSuccess) return rc;
             launch_eval_wide_dot(x, G, (int)n, (int)dp1, vmat, y, s);
             return ShareSuccess;
         }
-        const uint32_t* alpha;
-        ShareErrorCode rc = get_table(ctx, key("alpha", {n}, impl), [&] {
-            return gold ? build_alpha<HGl>(n, impl) : build_alpha<HFr>(n, impl);
-        }, &alpha);
-        if (rc != ShareSuccess) return rc;
-        launch_eval_wide(impl, x, G, (int)n, (int)dp1, alpha, y, s);
-        return ShareSuccess;
-    }
-    // mid-size batches on small domains as well: up to two tiles per workgroup the workgroup-per-tile matrix-core kernel
-    // beats the single-pass FFT on latency -- n = 16, d = 5: 5.8 us against 12.3 us at 2 100 .. 4 096 chunks, 8.4 against
-    // 13.3 at 16 384 (profiles/r02_team_kernel_encode.txt); at 2^20 the two tie
-    if (impl == IMPL_U29 && size <= 16 && ctx->matrix_cores && ctx->mfma_team && !ctx->force_generic && y.parties == 1 && dp1 >= 2 &&
-        dp1 <= MF_MAX_M && G >= ctx->mfma_min_encode && (G + 31) / 32 <= (size_t)(ctx->mfma_wgs ? ctx->mfma_wgs : ctx->n_cus) * 2 &&
-        try_mfma_eval(ctx, x, G, n, dp1, y, s, &rc_mf))
-        return rc_mf;
-    // large batches on small domains: with the points taken in pairs the matrix-core encode is ahead of the single-pass FFT
-    if (impl == IMPL_U29 && size <= 16 && size >= 8 && ctx->matrix_cores && ctx->mfma_bfly && !ctx->force_generic && y.parties <= 64 &&
-        dp1 >= 2 && dp1 <= MF_BFLY_MAX_M && (G + 31) / 32 > (size_t)(ctx->mfma_wgs ? ctx->mfma_wgs : ctx->n_cus) * 2 &&
-        G * std::max(dp1, (size_t)1) * 32 < ((size_t)1 << 32) && try_mfma_eval(ctx, x, G, n, dp1, y, s, &rc_mf))
-        return rc_mf;
-    // several parties' mid-size batches: one launch over all of them (the dealers' encodes of the producers)
-    if (party_batched_one_launch(ctx, G, n, dp1, y) && try_mfma_eval(ctx, x, G, n, dp1, y, s, &rc_mf)) return rc_mf;
-    if ((impl == IMPL_U29 || gold) && size <= 16 && !ctx->force_generic) {
-        const uint32_t* tw;
-        ShareErrorCode rc = get_table(ctx, key("tw", {size}, impl), [&] {
-            return gold ? build_twiddles<HGl>(size, impl) : build_twiddles<HFr>(size, impl);
-        }, &tw);
-        if (rc != ShareSuccess) return rc;
-        const int lg = ilog2(size), c = (int)dp1, nn = (int)n;
-        if (gold ? launch_gold_fft1(lg, c, x, G, nn, tw, y, s)
-                 : (lg < 4 ? launch_fft1_lo(lg, c, x, G, nn, tw, y, s)
-                           : (launch_fft1_16a(c, x, G, nn, tw, y, s) || launch_fft1_16b(c, x, G, nn, tw, y, s) ||
-                              launch_fft1_16c(c, x, G, nn, tw, y, s) || launch_fft1_16d(c, x, G, nn, tw, y, s))))
+        case EncodeKernel::Wide:
+        case EncodeKernel::Generic: {
+            const uint32_t* alpha;
+            rc = get_table(ctx, key("alpha", {n}, impl), [&] { return gold ? build_alpha<HGl>(n, impl) : build_alpha<HFr>(n, impl); }, &alpha);
+            if (rc != ShareSuccess) return rc;
+            if (r.kernel == EncodeKernel::Wide) launch_eval_wide(impl, x, G, (int)n, (int)dp1, alpha, y, s);
+            else launch_eval_generic(impl, x, G, (int)n, (int)dp1, alpha, y, s);
             return ShareSuccess;
-    } else if (impl == IMPL_U29 && ctx->matrix_cores && !ctx->force_generic && y.parties <= 64 && dp1 >= 2 &&
-               dp1 <= (ctx->mfma_bfly ? MF_BFLY_MAX_M : MF_MAX_M) && G >= ctx->mfma_min_encode && G * dp1 * 32 < ((size_t)1 << 32) && n <= 255 &&
-               try_mfma_eval(ctx, x, G, n, dp1, y, s, &rc_mf)) {
-        // domains beyond 16 points: the dense n x (d + 1) map on the matrix cores beats the multi-pass FFT (config 3's
-        // encode: 0.45 ms against 0.62 ms); up to 16 points the single-pass FFT stays (config 2: a tie at 0.187 ms)
-        return rc_mf;
-    } else if (gold && ctx->matrix_cores && !ctx->force_generic && y.parties <= 64 && dp1 >= 2 && dp1 <= MFGL_MAX_M &&
-               G >= ctx->mfma_min_gold && n <= 255 && try_mfma_eval_gl(ctx, x, G, n, dp1, y, s, &rc_mf)) {
-        return rc_mf;
-    } else if ((impl == IMPL_U29 || gold) && size <= 256 && dp1 <= 32 && !ctx->force_generic) {
-        const size_t P = size / 16;
-        const uint32_t *tw16, *twist;
-        ShareErrorCode rc = get_table(ctx, key("tw", {16}, impl), [&] {
-            return gold ? build_twiddles<HGl>(16, impl) : build_twiddles<HFr>(16, impl);
-        }, &tw16);
-        if (rc != ShareSuccess) return rc;
-        rc = get_table(ctx, key("twist", {size, dp1}, impl), [&] {
-            return gold ? build_twist<HGl>(size, P, dp1, impl) : build_twist<HFr>(size, P, dp1, impl);
-        }, &twist);
-        if (rc != ShareSuccess) return rc;
-        const int c = (int)dp1, nn = (int)n, pp = (int)P;
-        if (gold ? launch_gold_fftP(c, x, G, nn, pp, tw16, twist, y, s)
-                 : (launch_fftP_a(c, x, G, nn, pp, tw16, twist, y, s) || launch_fftP_b(c, x, G, nn, pp, tw16, twist, y, s) ||
-                    launch_fftP_c(c, x, G, nn, pp, tw16, twist, y, s) || launch_fftP_d(c, x, G, nn, pp, tw16, twist, y, s) ||
-                    launch_fftP_fold(c, x, G, nn, pp, tw16, twist, y, s)))
-            return ShareSuccess;
+        }
+        case EncodeKernel::MfmaRowsTeam:
+        case EncodeKernel::MfmaRows:
+        case EncodeKernel::Bfly:
+        case EncodeKernel::BflyParties:
+            if (run_mfma(ctx, r, x, G, n, dp1, y, s, &rc)) return rc;
+            break;
+        case EncodeKernel::MfmaRowsGl:
+            if (run_mfma_gl(ctx, x, G, n, dp1, y, s, &rc)) return rc;
+            break;
+        case EncodeKernel::Fft1: {
+            const uint32_t* tw;
+            rc = get_table(ctx, key("tw", {size}, impl), [&] { return gold ? build_twiddles<HGl>(size, impl) : build_twiddles<HFr>(size, impl); }, &tw);
+            if (rc != ShareSuccess) return rc;
+            const int lg = ilog2(size), c = (int)dp1, nn = (int)n;
+            if (gold ? launch_gold_fft1(lg, c, x, G, nn, tw, y, s)
+                     : lg < 4 ? launch_fft1_lo(lg, c, x, G, nn, tw, y, s) : launch_fft1_16(c, x, G, nn, tw, y, s))
+                return ShareSuccess;
+            break;
+        }
+        case EncodeKernel::FftP: {
+            const size_t P = size / 16;
+            const uint32_t *tw16, *twist;
+            rc = get_table(ctx, key("tw", {16}, impl), [&] { return gold ? build_twiddles<HGl>(16, impl) : build_twiddles<HFr>(16, impl); }, &tw16);
+            if (rc != ShareSuccess) return rc;
+            rc = get_table(ctx, key("twist", {size, dp1}, impl), [&] {
+                return gold ? build_twist<HGl>(size, P, dp1, impl) : build_twist<HFr>(size, P, dp1, impl);
+            }, &twist);
+            if (rc != ShareSuccess) return rc;
+            const int c = (int)dp1, nn = (int)n, pp = (int)P;
+            if (gold ? launch_gold_fftP(c, x, G, nn, pp, tw16, twist, y, s) : launch_fftP(c, x, G, nn, pp, tw16, twist, y, s)) return ShareSuccess;
+            break;
+        }
+        default:
+            break;
+        }
     }
-    const uint32_t* alpha;
-    ShareErrorCode rc = get_table(ctx, key("alpha", {n}, impl), [&] {
-        return impl == IMPL_GOLD ? build_alpha<HGl>(n, impl) : build_alpha<HFr>(n, impl);
-    }, &alpha);
-    if (rc != ShareSuccess) return rc;
-    launch_eval_generic(impl, x, G, (int)n, (int)dp1, alpha, y, s);
-    return ShareSuccess;
+    return fail(ctx, InvalidInput, "no encode kernel for this shape");  // not reached: the generic kernel ends every plan
 }
 
 static ShareErrorCode eval_dev(hbmpc_ctx* ctx, const void* x, size_t G, size_t n, size_t d, void* y, void* stream,
@@ -1374,36 +1314,24 @@ static ShareErrorCode triple_encode_any(hbmpc_ctx* ctx, const void* a, const voi
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = pick(ctx, stream);
     const size_t size = domain_size(n), dp1 = d + 1;
-    // small batches with a workspace: the product kernel + the wave-per-chunk evaluation are two short launches, the fused
-    // kernel one long one (a lane walks ~12 k instructions for its chunk): 1100 triples x 16 parties, the whole triple
-    // generation 0.043 ms against 0.057 ms
-    const bool small_two = tmp && G * parties <= ctx->wide_max_chunks / 4;
-    // Large batches on 9 .. 32 points: the products are computed inside the matrix-core encode with the points in pairs
-    // (k_mfma_bfly<.., TRIPLE>, kernels_mfma_bfly.hpp) -- config 4's 16 parties x 381 300 chunks: 2.22 - 2.28 ms against
-    // 2.53 - 2.55 of the fused FFT kernel on the same box (profiles/r03_mfma_bfly_triple.txt).  From 2^14 chunks over all parties: at the
-    // reference node's batch of 4 096 chunks x 16 parties the whole TripleGen step takes 0.073 ms against 0.093 with the lane kernel, a tie
-    // at 2^14 (profiles/r04_protocol_batch_sizes.txt)
-    if (ctx->impl == IMPL_U29 && ctx->matrix_cores && ctx->mfma_bfly && !ctx->force_generic && dp1 >= 2 && dp1 <= MF_MAX_M && size >= 16 &&
-        size <= 32 && n > size / 2 && G * parties >= ((size_t)1 << 14) && G * dp1 * 32 < ((size_t)1 << 32) && parties <= 65535) {
-        const size_t half = size / 2;
-        mf::MfmaRowsArgs ma;
-        memset(&ma, 0, sizeof ma);
-        const int nwg = ctx->mfma_wgs ? ctx->mfma_wgs : ctx->n_cus;
-        if (half * mf_bfly_row_bytes(dp1) <= 160 * 1024 && mf::mf_plan_pairs((int)half, (int)half, nwg, &ma)) {
+    EncodeShape shape{EncodeKind::Triple, G, n, d, parties};
+    shape.workspace = tmp != nullptr;
+    const EncodePlan plan = plan_encode(encode_knobs(ctx), shape);
+    for (int i = 0; i < plan.count; ++i) {
+        const EncodeRoute& r = plan.route[i];
+        if (r.kernel == EncodeKernel::BflyTriple) {
+            mf::MfmaRowsArgs ma;
+            memset(&ma, 0, sizeof ma);
+            mf::mf_take_plan(r.plan, &ma);
+            const size_t half = size / 2;
             const uint32_t* tab;
             std::array<size_t, 5> aux = {0, 0, 0, 0, 0};  // aux[0]: the table's words (0: the digit-sum bound could not be proved)
             // rows alpha_j^i R, R = 2^261: the kernel hands over (a b - r2t) / R (one Montgomery reduction, no conversions)
             ShareErrorCode rc = get_table(ctx, key("mfbflyR", {n, dp1}, ctx->impl), [&] {
-                std::vector<HFr> el = domain_elements<HFr>(n, n);
                 HFr R = HFr::one();
                 const HFr two = HFr::from_u64(2);
-                for (int i = 0; i < 261; ++i) R = R * two;
-                std::vector<std::vector<HFr>> V(n, std::vector<HFr>(dp1));
-                for (size_t j = 0; j < n; ++j) {
-                    HFr p = R;
-                    for (size_t k = 0; k < dp1; ++k) V[j][k] = p, p = p * el[j];
-                }
-                std::vector<uint32_t> tbl = build_mfma_bfly_table(V, dp1, half);
+                for (int e = 0; e < 261; ++e) R = R * two;
+                std::vector<uint32_t> tbl = build_mfma_bfly_table(vandermonde<HFr>(n, dp1, R), dp1, half);
                 aux[0] = tbl.size();
                 return tbl;
             }, &tab, &aux);
@@ -1412,33 +1340,26 @@ static ShareErrorCode triple_encode_any(hbmpc_ctx* ctx, const void* a, const voi
             ma.parties = (int)parties, ma.G = G, ma.in_chunk_major = 1, ma.nv = 0;
             ma.table = (const uint8_t*)tab, ma.half = (int)half, ma.nout = (int)n;
             ma.out = (uint8_t*)y, ma.out_party_major = 1, ma.out_stride = G;
-            const int mi = (int)dp1;
-            if (aux[0] != 0 && (launch_mfma_bfly_a(mi, ma, ctx->device, s) || launch_mfma_bfly_b(mi, ma, ctx->device, s) ||
-                                launch_mfma_bfly_c(mi, ma, ctx->device, s) || launch_mfma_bfly_d(mi, ma, ctx->device, s))) {
+            if (aux[0] != 0 && launch_mfma_bfly((int)dp1, ma, ctx->device, s)) {
+                HIP_TRY(ctx, hipGetLastError());
+                return ShareSuccess;
+            }
+        } else if (r.kernel == EncodeKernel::Fft1Triple) {
+            const bool gold = is_gold(ctx);
+            const uint32_t* tw;
+            ShareErrorCode rc = get_table(ctx, key("tw", {size}, ctx->impl), [&] {
+                return gold ? build_twiddles<HGl>(size, ctx->impl) : build_twiddles<HFr>(size, ctx->impl);
+            }, &tw);
+            if (rc != ShareSuccess) return rc;
+            const EvalOut out{WO(y), 0, (unsigned)parties};
+            if (gold ? launch_fft1_triple_gold(ilog2(size), (int)dp1, W(a), W(b), W(r2t), G, (int)n, tw, out, s)
+                     : launch_fft1_triple(ilog2(size), (int)dp1, W(a), W(b), W(r2t), G, (int)n, tw, out, elem_consts(ctx->impl).r2, s)) {
                 HIP_TRY(ctx, hipGetLastError());
                 return ShareSuccess;
             }
         }
     }
-    if (!small_two && ctx->impl == IMPL_U29 && size <= 16 && !ctx->force_generic) {
-        const uint32_t* tw;
-        ShareErrorCode rc = get_table(ctx, key("tw", {size}, ctx->impl), [&] { return build_twiddles<HFr>(size, ctx->impl); }, &tw);
-        if (rc != ShareSuccess) return rc;
-        const ElemConsts cs = elem_consts(ctx->impl);
-        if (launch_fft1_triple(ilog2(size), (int)dp1, W(a), W(b), W(r2t), G, (int)n, tw, EvalOut{WO(y), 0, (unsigned)parties}, cs.r2, s)) {
-            HIP_TRY(ctx, hipGetLastError());
-            return ShareSuccess;
-        }
-    }
-    if (ctx->impl == IMPL_GOLD && size <= 16 && !ctx->force_generic) {
-        const uint32_t* tw;
-        ShareErrorCode rc = get_table(ctx, key("tw", {size}, ctx->impl), [&] { return build_twiddles<HGl>(size, ctx->impl); }, &tw);
-        if (rc != ShareSuccess) return rc;
-        if (launch_fft1_triple_gold(ilog2(size), (int)dp1, W(a), W(b), W(r2t), G, (int)n, tw, EvalOut{WO(y), 0, (unsigned)parties}, s)) {
-            HIP_TRY(ctx, hipGetLastError());
-            return ShareSuccess;
-        }
-    }
+    // the last candidate (EncodeKernel::LocalProduct): the products into the workspace, then the chunk-major encode
     if (!tmp) return fail(ctx, InvalidInput, "no fused kernel for this shape: pass a workspace of parties * G * (d + 1) elements");
     ShareErrorCode rc = triple_local_any(ctx, a, b, r2t, parties * G * dp1, tmp, stream);
     if (rc != ShareSuccess) return rc;
@@ -1795,38 +1716,8 @@ static ShareErrorCode eval_rows_any(hbmpc_ctx* ctx, const void* x_rows, size_t x
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = pick(ctx, stream);
     const size_t size = domain_size(n), dp1 = d + 1;
-    ShareErrorCode rc_mf = ShareSuccess;
-    const bool mf_shape = ctx->impl == IMPL_U29 && ctx->matrix_cores && ctx->mfma_bfly && !ctx->force_generic && dp1 >= 2 && dp1 <= MF_BFLY_MAX_M &&
-                          size >= 8 && n <= 255 && (G + 31) / 32 > (size_t)(ctx->mfma_wgs ? ctx->mfma_wgs : ctx->n_cus) * 2 && G * 32 < ((size_t)1 << 32);
     if (lists && lists->others && (lists->rows >= n || (G / lists->K) * (n - lists->rows) * lists->K * 32 >= ((size_t)1 << 32)))
         return fail(ctx, InvalidInput, "party-major other rows: needs a row outside the lists and less than 4 GiB of them");
-    // the list rows straight from the kernel that computes them (k_mfma_bfly<.., LISTS>): one role, G < 2^32 chunks
-    if (lists && mf_shape && ctx->list_rows_in_kernel && try_mfma_eval(ctx, (const uint32_t*)x_rows, G, n, dp1, EvalOut{(uint32_t*)y, 0, 1}, s, &rc_mf, x_row_stride, lists)) {
-        if (rc_mf != ShareSuccess) return rc_mf;
-        HIP_TRY(ctx, hipGetLastError());
-        return ShareSuccess;
-    }
-    // Goldilocks, n inputs as rows, a domain of 4 .. 16 points: the single-pass lane kernel reads the rows in place and writes the lists and the
-    // party-major rows itself (k_eval_fft1_mix) -- one launch instead of a transpose either side of the encode
-    // (over Fr the same kernel on domains of 4 and 8 points -- 3 .. 8 parties -- where the matrix-core list kernel above did not take the call)
-    const bool mix_gl = is_gold(ctx) && size <= 16, mix_fr = ctx->impl == IMPL_U29 && size <= 8;
-    if (lists && (mix_gl || mix_fr) && ctx->list_rows_in_kernel && !ctx->force_generic && dp1 == n && n >= 3) {
-        const uint32_t* tw;
-        const ShareErrorCode rc = get_table(ctx, key("tw", {size}, ctx->impl), [&] {
-            return mix_gl ? build_twiddles<HGl>(size, ctx->impl) : build_twiddles<HFr>(size, ctx->impl);
-        }, &tw);
-        if (rc != ShareSuccess) return rc;
-        MixOut o;
-        memset(&o, 0, sizeof o);
-        o.y = (uint32_t*)y, o.others = (uint32_t*)lists->others, o.K = lists->K, o.row0 = (int)lists->row0, o.rows = (int)lists->rows;
-        for (size_t k = 0; k < lists->n_slices; ++k)
-            o.list[k] = MixOut::Slice{(uint32_t*)lists->slices[k].dst_dev, lists->slices[k].party_stride, lists->slices[k].k0, lists->slices[k].count};
-        if (mix_gl ? launch_gold_fft1_mix(ilog2(size), (int)dp1, (const uint32_t*)x_rows, x_row_stride, G, (int)n, tw, o, s)
-                   : launch_fft1_mix_lo(ilog2(size), (int)dp1, (const uint32_t*)x_rows, x_row_stride, G, (int)n, tw, o, s)) {
-            HIP_TRY(ctx, hipGetLastError());
-            return ShareSuccess;
-        }
-    }
     auto copy_lists = [&]() -> ShareErrorCode {  // every row is in y[row][G]: the list rows are copied out per slice
         if (!lists) return ShareSuccess;
         const size_t parties = G / lists->K;
@@ -1843,11 +1734,40 @@ static ShareErrorCode eval_rows_any(hbmpc_ctx* ctx, const void* x_rows, size_t x
         }
         return ShareSuccess;
     };
-    if (mf_shape && try_mfma_eval(ctx, (const uint32_t*)x_rows, G, n, dp1, EvalOut{(uint32_t*)y, 0, 1}, s, &rc_mf, x_row_stride)) {
-        if (rc_mf != ShareSuccess) return rc_mf;
-        HIP_TRY(ctx, hipGetLastError());
-        return copy_lists();
+    EncodeShape shape{EncodeKind::Rows, G, n, d};
+    shape.lists = lists != nullptr;
+    const EncodePlan plan = plan_encode(encode_knobs(ctx), shape);
+    for (int i = 0; i < plan.count; ++i) {
+        const EncodeRoute& r = plan.route[i];
+        ShareErrorCode rc = ShareSuccess;
+        if (r.kernel == EncodeKernel::BflyLists || r.kernel == EncodeKernel::Bfly) {
+            // the list rows straight from the kernel that computes them, or every row to y and the lists copied out
+            const bool in_kernel = r.kernel == EncodeKernel::BflyLists;
+            if (run_mfma(ctx, r, (const uint32_t*)x_rows, G, n, dp1, EvalOut{(uint32_t*)y, 0, 1}, s, &rc, x_row_stride, in_kernel ? lists : nullptr)) {
+                if (rc != ShareSuccess) return rc;
+                HIP_TRY(ctx, hipGetLastError());
+                return in_kernel ? ShareSuccess : copy_lists();
+            }
+        } else if (r.kernel == EncodeKernel::Fft1Mix) {
+            const bool gold = is_gold(ctx);
+            const uint32_t* tw;
+            rc = get_table(ctx, key("tw", {size}, ctx->impl), [&] {
+                return gold ? build_twiddles<HGl>(size, ctx->impl) : build_twiddles<HFr>(size, ctx->impl);
+            }, &tw);
+            if (rc != ShareSuccess) return rc;
+            MixOut o;
+            memset(&o, 0, sizeof o);
+            o.y = (uint32_t*)y, o.others = (uint32_t*)lists->others, o.K = lists->K, o.row0 = (int)lists->row0, o.rows = (int)lists->rows;
+            for (size_t k = 0; k < lists->n_slices; ++k)
+                o.list[k] = MixOut::Slice{(uint32_t*)lists->slices[k].dst_dev, lists->slices[k].party_stride, lists->slices[k].k0, lists->slices[k].count};
+            if (gold ? launch_gold_fft1_mix(ilog2(size), (int)dp1, (const uint32_t*)x_rows, x_row_stride, G, (int)n, tw, o, s)
+                     : launch_fft1_mix_lo(ilog2(size), (int)dp1, (const uint32_t*)x_rows, x_row_stride, G, (int)n, tw, o, s)) {
+                HIP_TRY(ctx, hipGetLastError());
+                return ShareSuccess;
+            }
+        }
     }
+    // the last candidate (EncodeKernel::Transpose): the rows into the workspace chunk-major, then the chunk-major encode
     if (!tmp) return fail(ctx, InvalidInput, "no kernel reads this shape from rows: pass a workspace of G * (d + 1) elements");
     if ((dp1 + 15) / 16 > 65535) return fail(ctx, InvalidInput, "d beyond the launch grid");
     launch_transpose(is_gold(ctx) ? 1 : 4, (const uint64_t*)x_rows, dp1, G, x_row_stride, (uint64_t*)tmp, dp1, 1, 0, 0, s);
@@ -1875,18 +1795,7 @@ static ShareErrorCode eval_rows_lists_any(hbmpc_ctx* ctx, const void* x_rows, si
 // would the mixing step write its lists (and party-major other rows) from the kernel that computes them?  (otherwise: all rows to y, then copies)
 extern "C" ShareErrorCode hbmpc_dev_apply_rows_lists_in_kernel(hbmpc_ctx* ctx, size_t G, size_t n, size_t d, int* yes_out) {
     if (!ctx || !yes_out) return InvalidInput;
-    const size_t size = domain_size(n), dp1 = d + 1;
-    if (is_gold(ctx)) {  // k_eval_fft1_mix: the n x n mixing step on domains of up to 16 points, any batch size
-        *yes_out = ctx->list_rows_in_kernel && !ctx->force_generic && dp1 == n && size <= 16 && n >= 3;
-        return ShareSuccess;
-    }
-    if (ctx->impl == IMPL_U29 && ctx->list_rows_in_kernel && !ctx->force_generic && dp1 == n && size <= 8 && n >= 3) {  // the same kernel over Fr, 3 .. 8 parties
-        *yes_out = 1;
-        return ShareSuccess;
-    }
-    *yes_out = ctx->impl == IMPL_U29 && ctx->matrix_cores && ctx->mfma_bfly && !ctx->force_generic && ctx->list_rows_in_kernel && dp1 >= 2 &&
-               dp1 >= 5 && dp1 <= MF_BFLY_MAX_M && size >= 8 && size <= 16 && n > size / 2 &&  // tu_mfma_bfly.inc: launch_lists
-               (G + 31) / 32 > (size_t)(ctx->mfma_wgs ? ctx->mfma_wgs : ctx->n_cus) * 2 && G * 32 < ((size_t)1 << 32);
+    *yes_out = encode_lists_in_kernel(encode_knobs(ctx), G, n, d);
     return ShareSuccess;
 }
 extern "C" ShareErrorCode hbmpc_dev_vandermonde_apply_rows_split(hbmpc_ctx* ctx, const U256* x_rows_dev, size_t x_row_stride, size_t G, size_t n, size_t d,

@@ -29,6 +29,7 @@
 
 #include "fr_u29.hpp"
 #include "kernels_recover.hpp"
+#include "mfma_plan.hpp"
 
 namespace hbmpc {
 namespace mf {
@@ -226,10 +227,6 @@ HB_DEV void mfma_row(const uint8_t* tab_lane, const v4i (&data)[CG][M], v16i (&a
     }
 }
 
-struct MfmaRole {
-    int row0, nrows;  // rows [row0, row0 + nrows) of the table
-};
-constexpr int MF_MAX_ROLES = 4;
 struct MfmaRowsArgs {
     // input: M elements per chunk
     const uint8_t* in;
@@ -508,63 +505,6 @@ __global__ __launch_bounds__(64 * WAVES) void k_mfma_rows(MfmaRowsArgs a) {
     if (a.direct) finish_direct(a.counters, a.summary);
 }
 
-// nwg workgroups (rounded down to blocks of 8, at most 64 blocks) shared among the roles already in a->role[0 .. a->nroles)
-// in proportion to their rows
-inline bool mf_deal_blocks(int rows, int nwg, MfmaRowsArgs* a) {
-    const int nroles = a->nroles;
-    int nblocks = nwg / 8;
-    nblocks = nblocks > 64 ? 64 : nblocks < nroles ? nroles : nblocks;
-    a->nblocks = nblocks;
-    // blocks per role in proportion to its rows (at least one), dealt out by largest remaining deficit
-    int have[MF_MAX_ROLES] = {0, 0, 0, 0};
-    for (int j = 0; j < nblocks; ++j) {
-        int best = 0;
-        double bestd = -1e30;
-        for (int k = 0; k < nroles; ++k) {
-            const double want = (double)(j + 1) * a->role[k].nrows / rows;
-            const double dfc = have[k] == 0 && nblocks - j <= nroles ? 1e9 : want - have[k];  // nobody is left without a block
-            if (dfc > bestd) bestd = dfc, best = k;
-        }
-        a->blk_role[j] = (uint8_t)best;
-        a->blk_idx[j] = (uint8_t)have[best]++;
-    }
-    for (int k = 0; k < nroles; ++k) {
-        if (have[k] == 0) return false;
-        a->role_nwg[k] = have[k] * 8;
-    }
-    return true;
-}
-// Host side: cut `rows` table rows (the first nv of them verify rows) into roles of at most `cap` rows.  Everything in one
-// role when it fits; otherwise the verify rows form role 0 and the output rows are cut evenly into as few roles as
-// possible.  nwg workgroups (rounded down to blocks of 8, at most 64 blocks) are shared in proportion to the rows.
-// Returns false when the verify rows do not fit one role (the caller then uses the lane-per-chunk kernels).
-inline bool mf_plan_roles(int rows, int nv, int cap, int nwg, MfmaRowsArgs* a) {
-    if (cap < 1 || nv > cap || rows < 1) return false;
-    int nroles = 0;
-    if (rows <= cap) {
-        a->role[nroles++] = MfmaRole{0, rows};
-    } else {
-        if (nv > 0) a->role[nroles++] = MfmaRole{0, nv};
-        const int ow = rows - nv, parts = (ow + cap - 1) / cap, per = (ow + parts - 1) / parts;
-        for (int r = nv; r < rows; r += per) {
-            if (nroles == MF_MAX_ROLES) return false;
-            a->role[nroles++] = MfmaRole{r, rows - r < per ? rows - r : per};
-        }
-    }
-    a->nroles = nroles;
-    return mf_deal_blocks(rows, nwg, a);
-}
-// the point pairs of kernels_mfma_bfly.hpp: `pairs` (a power of two) table rows in roles of EQUAL size, the largest power
-// of two that fits `cap` rows -- the kernel's unrolled pair loop has one trip count for every workgroup of a launch
-inline bool mf_plan_pairs(int pairs, int cap, int nwg, MfmaRowsArgs* a) {
-    if (cap < 1 || pairs < 1 || (pairs & (pairs - 1)) != 0) return false;
-    int per = pairs;
-    while (per > cap) per >>= 1;
-    if (per < 1 || pairs / per > MF_MAX_ROLES) return false;
-    a->nroles = pairs / per;
-    for (int k = 0; k < a->nroles; ++k) a->role[k] = MfmaRole{k * per, per};
-    return mf_deal_blocks(pairs, nwg, a);
-}
 inline int mf_grid(const MfmaRowsArgs& a) { return 8 * a.nblocks; }
 inline int mf_max_role_rows(const MfmaRowsArgs& a) {
     int m = 0;

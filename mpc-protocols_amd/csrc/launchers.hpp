@@ -37,6 +37,10 @@ bool launch_fft1_16a(int cnt, const uint32_t* x, size_t G, int n, const uint32_t
 bool launch_fft1_16b(int cnt, const uint32_t* x, size_t G, int n, const uint32_t* tw, EvalOut y, hipStream_t s);
 bool launch_fft1_16c(int cnt, const uint32_t* x, size_t G, int n, const uint32_t* tw, EvalOut y, hipStream_t s);
 bool launch_fft1_16d(int cnt, const uint32_t* x, size_t G, int n, const uint32_t* tw, EvalOut y, hipStream_t s);
+inline bool launch_fft1_16(int cnt, const uint32_t* x, size_t G, int n, const uint32_t* tw, EvalOut y, hipStream_t s) {
+    return launch_fft1_16a(cnt, x, G, n, tw, y, s) || launch_fft1_16b(cnt, x, G, n, tw, y, s) || launch_fft1_16c(cnt, x, G, n, tw, y, s) ||
+           launch_fft1_16d(cnt, x, G, n, tw, y, s);
+}
 // triple_gen's local product fused into the encode (k_eval_fft1_triple); false when the shape is not instantiated
 bool launch_fft1_triple(int lg, int cnt, const uint32_t* a, const uint32_t* b, const uint32_t* r2t, size_t G, int n,
                         const uint32_t* tw, EvalOut y, const uint32_t r2[9], hipStream_t s);
@@ -53,6 +57,12 @@ bool launch_fftP_d(int dp1, const uint32_t* x, size_t G, int n, int P, const uin
                    EvalOut y, hipStream_t s);
 bool launch_fftP_fold(int dp1, const uint32_t* x, size_t G, int n, int P, const uint32_t* tw16, const uint32_t* twist,
                       EvalOut y, hipStream_t s);
+inline bool launch_fftP(int dp1, const uint32_t* x, size_t G, int n, int P, const uint32_t* tw16, const uint32_t* twist, EvalOut y,
+                        hipStream_t s) {
+    return launch_fftP_a(dp1, x, G, n, P, tw16, twist, y, s) || launch_fftP_b(dp1, x, G, n, P, tw16, twist, y, s) ||
+           launch_fftP_c(dp1, x, G, n, P, tw16, twist, y, s) || launch_fftP_d(dp1, x, G, n, P, tw16, twist, y, s) ||
+           launch_fftP_fold(dp1, x, G, n, P, tw16, twist, y, s);
+}
 // Goldilocks instantiations of the same templates
 bool launch_gold_fft1(int log, int cnt, const uint32_t* x, size_t G, int n, const uint32_t* tw, EvalOut y, hipStream_t s);
 bool launch_gold_fftP(int dp1, const uint32_t* x, size_t G, int n, int P, const uint32_t* tw16, const uint32_t* twist,
@@ -61,11 +71,15 @@ bool launch_gold_recover(int m, bool p0, const RecoverArgs& ra, unsigned grid, h
 // generic Horner evaluation (impl: 0 = U29, 1 = Sat32, 2 = Goldilocks)
 void launch_eval_generic(int impl, const uint32_t* x, size_t G, int n, int dp1, const uint32_t* alpha, EvalOut y,
                          hipStream_t s);
-// batch recover, U29, register-resident m <= 16
+// batch recover, U29, register-resident m <= 16 (launch_recover tries the four translation units)
 bool launch_recover_a(int m, bool p0, const RecoverArgs& ra, unsigned grid, hipStream_t s);
 bool launch_recover_b(int m, bool p0, const RecoverArgs& ra, unsigned grid, hipStream_t s);
 bool launch_recover_c(int m, bool p0, const RecoverArgs& ra, unsigned grid, hipStream_t s);
 bool launch_recover_d(int m, bool p0, const RecoverArgs& ra, unsigned grid, hipStream_t s);
+inline bool launch_recover(int m, bool p0, const RecoverArgs& ra, unsigned grid, hipStream_t s) {
+    return launch_recover_a(m, p0, ra, grid, s) || launch_recover_b(m, p0, ra, grid, s) || launch_recover_c(m, p0, ra, grid, s) ||
+           launch_recover_d(m, p0, ra, grid, s);
+}
 
 void launch_recover_generic(int impl, bool p0, const RecoverArgs& ra, unsigned grid, hipStream_t s);
 // matrix-core form of the constant-matrix maps (kernels_mfma.hpp), m = 2 .. 15; false when m is not instantiated there.
@@ -79,12 +93,20 @@ bool launch_mfma_rows_a(int m, const mf::MfmaRowsArgs& a, int device, hipStream_
 bool launch_mfma_rows_b(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s, bool team = false);
 bool launch_mfma_rows_c(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s, bool team = false);
 bool launch_mfma_rows_d(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s, bool team = false);
+inline bool launch_mfma_rows(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s, bool team = false) {
+    return launch_mfma_rows_a(m, a, device, s, team) || launch_mfma_rows_b(m, a, device, s, team) || launch_mfma_rows_c(m, a, device, s, team) ||
+           launch_mfma_rows_d(m, a, device, s, team);
+}
 // the encode on a domain of roots of unity with the points taken in pairs (k, k + size / 2): half the MFMAs (kernels_mfma_bfly.hpp);
 // with a.in_b set: the fused local product + encode of triple generation (one role of 8 or 16 pairs; false otherwise)
 bool launch_mfma_bfly_a(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s);
 bool launch_mfma_bfly_b(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s);
 bool launch_mfma_bfly_c(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s);
 bool launch_mfma_bfly_d(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s);
+inline bool launch_mfma_bfly(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s) {
+    return launch_mfma_bfly_a(m, a, device, s) || launch_mfma_bfly_b(m, a, device, s) || launch_mfma_bfly_c(m, a, device, s) ||
+           launch_mfma_bfly_d(m, a, device, s);
+}
 // small batches: one wave per chunk, one evaluation point / one table row per lane (k_eval_wide, k_batch_recover_wide)
 void launch_eval_wide(int impl, const uint32_t* x, size_t G, int n, int dp1, const uint32_t* alpha, EvalOut y, hipStream_t s);
 void launch_eval_wide_dot(const uint32_t* x, size_t G, int n, int dp1, const uint32_t* vmat, EvalOut y, hipStream_t s);  // U29, vmat [n][dp1] <= 48 KB
