@@ -50,8 +50,9 @@ typedef struct {
     uint64_t data[4];
 } U256;
 
-/* ffi/c_bindings/share/mod.rs:18-37 (same order, same values); the HBMPC_* values are new and
- * never produced by the reference: they report conditions the Rust code cannot have. */
+/* ffi/c_bindings/share/mod.rs:18-37 (same order, same values).  The HBMPC_* values are this library's: 100 and 101 report
+ * conditions the Rust code cannot have; 102 and 103 carry the two RandBitError variants of phase 2
+ * (fpmul/rand_bit.rs:197-220), which the reference reports through its own error type, not through ShareErrorCode. */
 typedef enum {
     ShareSuccess = 0,
     InsufficientShares = 1,
@@ -63,7 +64,9 @@ typedef enum {
     PolynomialOperationError = 7,
     DecodingError = 8,
     HBMPC_NO_DEVICE = 100,    /* no HIP device / HIP runtime error (see hbmpc_last_error) */
-    HBMPC_OUT_OF_MEMORY = 101 /* device allocation failed */
+    HBMPC_OUT_OF_MEMORY = 101, /* device allocation failed */
+    HBMPC_ZERO_SQUARE = 102,   /* RandBitError::ZeroSquare: an opened square a^2 is zero (rand_bit.rs:198-202) */
+    HBMPC_NO_SQUARE_ROOT = 103 /* RandBitError::SquareRoot: an opened square has no root (rand_bit.rs:206) */
 } ShareErrorCode;
 
 /* ffi/c_bindings/share/mod.rs:50-53 (FieldKind).  Goldilocks64 is this library's extension for the reference's small
@@ -86,6 +89,14 @@ typedef struct {
     uint32_t first_failed; /* lowest failing chunk index (valid when n_failed > 0)       */
     uint32_t first_error;  /* its ShareErrorCode: what the reference's `?` would return  */
 } hbmpc_recover_summary;
+
+/* verdict of one RandBit finalize (hbmpc_[gl_]dev_randbit_finalize_parties writes it to device memory) */
+typedef struct {
+    uint64_t first;    /* (status << 32) | index of the element the reference's error names (status 1 = zero square, 2 = no
+                        * root: the minimum over the failed elements, so a zero anywhere wins); all ones when none failed */
+    uint32_t n_failed; /* elements whose status is not 0 */
+    uint32_t reserved;
+} hbmpc_randbit_summary;
 
 /* ---- Device buffers ----------------------------------------------------------------------
  * Every *_dev pointer must be device memory that is coherent at kernel boundaries of a stream: hipMalloc (or an
@@ -203,6 +214,23 @@ ShareErrorCode hbmpc_pipe_ransha_create(hbmpc_ctx* ctx, size_t n, size_t t, size
                                         hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_randousha_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t K, void* stream, hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_preprocessing_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream, hbmpc_pipe** pipe_out);
+/* RandBit (fpmul/rand_bit.rs:242-293, 197-220) over either field: N random bits for n parties from N shared values a and one Beaver
+ * triple each.  N must be a multiple of t + 1 (rand_bit.rs:253-255: Incompatible; here InvalidInput), n >= 2t + 1.  run() is
+ *   Multiply::init(a, a, triples) (mul/multiplication.rs:417-462): d = ta - a, e = tb - a side by side
+ *       (hbmpc_[gl_]dev_beaver_open_shares_paired), opened by BatchRecon of degree t over the 2 N values: every party's encode
+ *       (hbmpc_[gl_]dev_vandermonde_apply_parties), the recipients' P(0) decodes and the coefficient decode of the revealed values
+ *       (hbmpc_[gl_]dev_batch_recover_strided, hbmpc_[gl_]dev_batch_recover), each from senders 0 .. 2t;
+ *   finalize_mul (multiplication.rs:57-100): [a^2] = tc - d e - d a - e a (hbmpc_[gl_]dev_beaver_finalize_parties);
+ *   BatchRecon of the [a^2] chunks of t + 1 (rand_bit.rs:281-290) the same way;
+ *   hbmpc_[gl_]dev_randbit_finalize_parties.
+ * The reference keys a chunk's BatchRecon session by a u8 sub_id (rand_bit.rs:284), so one of its sessions holds at most 256 chunks;
+ * every chunk is independent, so this pipeline's N elements give the bytes of ceil(N / (256 (t + 1))) such sessions.
+ * Buffers: a, ta, tb, tc (inputs [n][N]); out ([n][N]); sq ([n][N], the [a^2] shares); sqop ([N], the opened squares); status ([N]
+ * bytes, the finalize's); summary (hbmpc_randbit_summary); desh ([n][2][N]); Y, Z, deop ([2 N]: d then e); the decodes' status
+ * bytes and summaries rstatus_de, rstatus_sq ([n G] bytes), summary_de_first, summary_de, summary_sq_first, summary_sq (G: chunks
+ * of the open).  hbmpc_pipe_summary reads summary_sq.  Checked mode returns the first failing decode's error, else HBMPC_ZERO_SQUARE
+ * / HBMPC_NO_SQUARE_ROOT from the finalize's summary -- where the reference's `?` returns. */
+ShareErrorCode hbmpc_pipe_randbit_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream, hbmpc_pipe** pipe_out);
 void hbmpc_pipe_destroy(hbmpc_pipe* pipe);
 ShareErrorCode hbmpc_pipe_part(hbmpc_pipe* pipe, const char* name, hbmpc_pipe** part_out);
 ShareErrorCode hbmpc_pipe_buffer(hbmpc_pipe* pipe, const char* name, void** dev_out, size_t* elements_out);
@@ -778,6 +806,33 @@ ShareErrorCode hbmpc_gl_dev_beaver_finalize(hbmpc_ctx* ctx, const uint64_t* c, c
 ShareErrorCode hbmpc_gl_dev_beaver_open_shares_paired(hbmpc_ctx* ctx, const uint64_t* a, const uint64_t* b, const uint64_t* x,
                                                       const uint64_t* y, size_t N, size_t parties, uint64_t* de_sh_out,
                                                       void* stream);
+
+/* ==== square roots, inverses and RandBit's phase 2 (csrc/kernels_sqrt.hpp) ====================================================
+ * Field::sqrt and Field::inverse of ark-ff 0.5 for N elements (the ark-ff source is not part of this repository: the semantics are
+ * restated from its fields/sqrt.rs and tested against that restatement, tests/randbit_ref.py -- the choice between the two roots
+ * is as unpinned as the rest of the oracle).  sqrt: root_out = the root ark returns (Tonelli-Shanks with
+ * z = 7^T, p - 1 = 2^32 T; sqrt(0) = 0), has_root_out = 1, or root_out = 0 and has_root_out = 0 where ark returns None.
+ * inverse: inv_out = a^-1 and ok_out = 1, or 0 and 0 for a = 0.  Constant tables are built per context at the first call (run it
+ * once before a graph capture). */
+/* replaces Field::sqrt as rand_bit.rs:206 calls it */
+ShareErrorCode hbmpc_fr_sqrt(hbmpc_ctx* ctx, const U256* a, size_t N, U256* root_out, uint8_t* has_root_out);
+ShareErrorCode hbmpc_dev_fr_sqrt(hbmpc_ctx* ctx, const U256* a, size_t N, U256* root_out, uint8_t* has_root_out, void* stream);
+ShareErrorCode hbmpc_gl_fr_sqrt(hbmpc_ctx* ctx, const uint64_t* a, size_t N, uint64_t* root_out, uint8_t* has_root_out);
+ShareErrorCode hbmpc_gl_dev_fr_sqrt(hbmpc_ctx* ctx, const uint64_t* a, size_t N, uint64_t* root_out, uint8_t* has_root_out, void* stream);
+/* replaces Field::inverse as rand_bit.rs:207 calls it */
+ShareErrorCode hbmpc_fr_inverse(hbmpc_ctx* ctx, const U256* a, size_t N, U256* inv_out, uint8_t* ok_out);
+ShareErrorCode hbmpc_dev_fr_inverse(hbmpc_ctx* ctx, const U256* a, size_t N, U256* inv_out, uint8_t* ok_out, void* stream);
+ShareErrorCode hbmpc_gl_fr_inverse(hbmpc_ctx* ctx, const uint64_t* a, size_t N, uint64_t* inv_out, uint8_t* ok_out);
+ShareErrorCode hbmpc_gl_dev_fr_inverse(hbmpc_ctx* ctx, const uint64_t* a, size_t N, uint64_t* inv_out, uint8_t* ok_out, void* stream);
+/* RandBit phase 2 (rand_bit.rs:197-220) for `parties` parties in one launch: a [parties][N] the shares of a, opened_sq [N] the opened
+ * A = a^2.  out[p][i] = ([a]_p b^-1 + 1) 2^-1 with b = A.sqrt() (common/mod.rs:205-218,267-280: Mul<F>, Add<F>), computed as
+ * [a]_p s + 2^-1 with s = b^-1 2^-1 once per element -- the same field element, so the same bytes.  status_out[i] = 0 ok, 1 A = 0,
+ * 2 no root; a failed element's shares are zero for every party.  summary_dev (device memory, reset by the call) ranks the failures
+ * as the reference does: ZeroSquare if any A is zero, else SquareRoot at the first element without a root.  parties in 1..65535. */
+ShareErrorCode hbmpc_dev_randbit_finalize_parties(hbmpc_ctx* ctx, const U256* a, const U256* opened_sq, size_t N, size_t parties, U256* out,
+                                                  uint8_t* status_out, hbmpc_randbit_summary* summary_dev, void* stream);
+ShareErrorCode hbmpc_gl_dev_randbit_finalize_parties(hbmpc_ctx* ctx, const uint64_t* a, const uint64_t* opened_sq, size_t N, size_t parties,
+                                                     uint64_t* out, uint8_t* status_out, hbmpc_randbit_summary* summary_dev, void* stream);
 
 /* ---- A/B aid: 0 = unsaturated 9x29-bit limbs (default, fast), 1 = saturated 8x32-bit limbs
  * (the straightforward formulation; same results, kept as a cross-check). */

@@ -160,6 +160,36 @@ class RanDouSha : public Producer {
     }
 };
 
+// RandBit of N shared values for n parties (N a multiple of t + 1): Beaver square of a, BatchRecon of a^2, phase 2
+// (fpmul/rand_bit.rs:242-293,197-220).  Buffers a, ta, tb, tc (inputs), out (output), sq: [party][N]; sqop: [N].  Elements are
+// those of the context's field (U256, or 8-byte Goldilocks values: cast the pointers).  run(true) fails with HBMPC_ZERO_SQUARE /
+// HBMPC_NO_SQUARE_ROOT where phase 2's `?` returns; summary() gives the finalize's verdict.
+class RandBit : public Pipeline {
+  public:
+    RandBit(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream) : Pipeline(ctx, create(ctx, n, t, N, stream), stream) { bind(); }
+    U256 *a, *ta, *tb, *tc, *out, *sq, *sqop;
+    uint8_t* status;                        // [N]: 0 ok, 1 zero square, 2 no root
+    hbmpc_randbit_summary* summary_dev;     // device memory
+    hbmpc_randbit_summary summary() {
+        hbmpc_randbit_summary s;
+        pl_check(hbmpc_memcpy_d2h(ctx_, &s, summary_dev, sizeof s, stream_), ctx_, "summary");
+        pl_check(hbmpc_stream_sync(ctx_, stream_), ctx_, "sync");
+        return s;
+    }
+
+  private:
+    static hbmpc_pipe* create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream) {
+        hbmpc_pipe* h = nullptr;
+        pl_check(hbmpc_pipe_randbit_create(ctx, n, t, N, stream, &h), ctx, "hbmpc_pipe_randbit_create");
+        return h;
+    }
+    void bind() {
+        a = buffer("a"), ta = buffer("ta"), tb = buffer("tb"), tc = buffer("tc"), out = buffer("out"), sq = buffer("sq"), sqop = buffer("sqop");
+        status = reinterpret_cast<uint8_t*>(buffer("status"));
+        summary_dev = reinterpret_cast<hbmpc_randbit_summary*>(buffer("summary"));
+    }
+};
+
 // run_preprocessing's triple part for all n parties, device-resident from the dealers' polynomials to [c]_t
 class Preprocessing : public Pipeline {
   public:

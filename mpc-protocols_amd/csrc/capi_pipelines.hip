@@ -12,6 +12,7 @@
 //   randousha      DouShaNode deal + RanDouShaNode: both Vandermonde products, verifier interpolations + tests, output slice
 //                  double_share/double_share_generation.rs:151-215, ran_dou_sha/mod.rs:371-449,569-602,314-331
 //   preprocessing  run_preprocessing's triple part (honeybadger/mod.rs:1239-1393): ransha -> a, b; randousha -> r; triplegen
+//   randbit        RandBit: Beaver square of a, BatchRecon of a^2, phase 2   fpmul/rand_bit.rs:242-293,197-220
 //
 // Host-side orchestration only: this file is a CLIENT of the hbmpc_dev_* entry points (it includes nothing but the public
 // header); every arithmetic step is a device call, buffers never leave HBM, the parties' all-to-all is a layout.
@@ -497,6 +498,70 @@ struct Preprocessing : hbmpc_pipe {
     }
 };
 
+// RandBit of N shared values for n parties (fpmul/rand_bit.rs:242-293, 197-220; either field).  Both opens are BatchRecon of
+// degree t (N is a multiple of t + 1, so Multiply never takes the RBC path: mul/multiplication.rs:417-462): every party's encode of its
+// chunks of t + 1, the recipients' P(0) decodes from senders 0 .. 2t, the coefficient decode of the revealed values from the same.
+struct RandBit : hbmpc_pipe {
+    size_t n, t, N, Gde, Gsq;
+    unsigned char *a, *ta, *tb, *tc, *out, *sq, *sqop, *desh, *Y, *Z, *deop;
+    uint8_t *status, *rst_de, *rst_sq;
+    hbmpc_recover_summary *sm_de_first, *sm_de, *sm_sq_first;  // summ: summary_sq
+    hbmpc_randbit_summary* rb;
+    std::vector<size_t> ids;
+    RandBit(hbmpc_ctx* cx, size_t n_, size_t t_, size_t N_, void* s) : hbmpc_pipe(cx, s), n(n_), t(t_), N(N_) {
+        if (n == 0 || N == 0 || N % (t + 1) != 0 || n < 2 * t + 1) throw PipeError{InvalidInput};  // rand_bit.rs:253-255
+        Gde = 2 * N / (t + 1), Gsq = N / (t + 1);
+        arena((8 * n * N + n * n * Gde + n * Gde + 3 * N) * f.eb + N + 2 * n * Gde + (1 << 14));
+        a = take("a", n * N), ta = take("ta", n * N), tb = take("tb", n * N), tc = take("tc", n * N);
+        out = take("out", n * N), sq = take("sq", n * N);
+        desh = take("desh", 2 * n * N);  // [party][2][N]: ta - a, then tb - a
+        Y = take("Y", n * n * Gde);      // [party][recipient][chunk]: the encoded messages (both opens)
+        Z = take("Z", n * Gde);          // [recipient][chunk]: the revealed values
+        deop = take("deop", 2 * N);      // the opened d [N], then e [N]
+        sqop = take("sqop", N);
+        status = take_bytes("status", N, N);
+        rst_de = take_bytes("rstatus_de", n * Gde, n * Gde);
+        rst_sq = take_bytes("rstatus_sq", n * Gsq, n * Gsq);
+        rb = reinterpret_cast<hbmpc_randbit_summary*>(take_bytes("summary", 64, 16));
+        sm_de_first = reinterpret_cast<hbmpc_recover_summary*>(take_bytes("summary_de_first", 64, 16));
+        sm_de = reinterpret_cast<hbmpc_recover_summary*>(take_bytes("summary_de", 64, 16));
+        sm_sq_first = reinterpret_cast<hbmpc_recover_summary*>(take_bytes("summary_sq_first", 64, 16));
+        summ = reinterpret_cast<hbmpc_recover_summary*>(take_bytes("summary_sq", 64, 16));
+        for (size_t i = 0; i < 2 * t + 1; ++i) ids.push_back(i);
+    }
+    // BatchRecon (degree t) of x [party][G (t + 1)] -> opened [G (t + 1)] (batch_recon.rs:157-165, 384-391, 457-467)
+    void open(const unsigned char* x, size_t G, unsigned char* opened, uint8_t* st, hbmpc_recover_summary* first, hbmpc_recover_summary* second) {
+        PL(f.gl ? hbmpc_gl_dev_vandermonde_apply_parties(ctx, (const uint64_t*)x, G, n, t, n, (uint64_t*)Y, stream)
+                : hbmpc_dev_vandermonde_apply_parties(ctx, (const U256*)x, G, n, t, n, (U256*)Y, stream));
+        PL(f.recover_strided(ctx, ids.data(), ids.size(), Y, n * G, n * G, n, t, t, 1, Z, nullptr, st, first, stream));
+        check_summary(first);
+        PL(f.recover(ctx, ids.data(), ids.size(), Z, G, n, t, t, opened, nullptr, st, second, stream));
+        check_summary(second);
+    }
+    void run() override {
+        // Multiply::init(a, a, triples): d = ta - a, e = tb - a (multiplication.rs:417-426), opened together
+        PL(f.gl ? hbmpc_gl_dev_beaver_open_shares_paired(ctx, (const uint64_t*)ta, (const uint64_t*)tb, (const uint64_t*)a, (const uint64_t*)a, N, n,
+                                                         (uint64_t*)desh, stream)
+                : hbmpc_dev_beaver_open_shares_paired(ctx, (const U256*)ta, (const U256*)tb, (const U256*)a, (const U256*)a, N, n, (U256*)desh, stream));
+        open(desh, Gde, deop, rst_de, sm_de_first, sm_de);
+        // finalize_mul (multiplication.rs:57-100): [a^2] = tc - d e - d a - e a
+        const unsigned char* e = deop + N * f.eb;
+        PL(f.gl ? hbmpc_gl_dev_beaver_finalize_parties(ctx, (const uint64_t*)tc, (const uint64_t*)a, (const uint64_t*)a, (const uint64_t*)deop,
+                                                       (const uint64_t*)e, N, n, (uint64_t*)sq, stream)
+                : hbmpc_dev_beaver_finalize_parties(ctx, (const U256*)tc, (const U256*)a, (const U256*)a, (const U256*)deop, (const U256*)e, N, n,
+                                                    (U256*)sq, stream));
+        open(sq, Gsq, sqop, rst_sq, sm_sq_first, summ);  // rand_bit.rs:281-290
+        PL(f.gl ? hbmpc_gl_dev_randbit_finalize_parties(ctx, (const uint64_t*)a, (const uint64_t*)sqop, N, n, (uint64_t*)out, status, rb, stream)
+                : hbmpc_dev_randbit_finalize_parties(ctx, (const U256*)a, (const U256*)sqop, N, n, (U256*)out, status, rb, stream));
+        if (checked) {  // phase 2's `?` (rand_bit.rs:198-207)
+            hbmpc_randbit_summary v;
+            PL(hbmpc_memcpy_d2h(ctx, &v, rb, sizeof v, stream));
+            PL(hbmpc_stream_sync(ctx, stream));
+            if (v.n_failed != 0) throw PipeError{(v.first >> 32) == 1 ? HBMPC_ZERO_SQUARE : HBMPC_NO_SQUARE_ROOT};
+        }
+    }
+};
+
 template <class F>
 ShareErrorCode guarded(F&& fn) {
     try {
@@ -533,6 +598,9 @@ extern "C" ShareErrorCode hbmpc_pipe_randousha_create(hbmpc_ctx* ctx, size_t n, 
 }
 extern "C" ShareErrorCode hbmpc_pipe_preprocessing_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream, hbmpc_pipe** pipe_out) {
     return create<Preprocessing>(ctx, pipe_out, n, t, N, stream);
+}
+extern "C" ShareErrorCode hbmpc_pipe_randbit_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream, hbmpc_pipe** pipe_out) {
+    return create<RandBit>(ctx, pipe_out, n, t, N, stream);
 }
 extern "C" void hbmpc_pipe_destroy(hbmpc_pipe* pipe) { delete pipe; }
 extern "C" ShareErrorCode hbmpc_pipe_part(hbmpc_pipe* pipe, const char* name, hbmpc_pipe** part_out) {

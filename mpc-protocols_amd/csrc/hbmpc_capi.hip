@@ -27,6 +27,8 @@
 #include "kernels_mfma.hpp"
 #include "kernels_mfma_gl.hpp"
 #include "encode_route.hpp"
+#include "kernels_sqrt.hpp"
+#include "tables_sqrt.hpp"
 
 using namespace hbmpc;
 
@@ -1454,6 +1456,111 @@ TYPED_PAIR(uint64_t, REQ_GL, hbmpc_gl_)
     }
 TYPED_PARTIES(U256, REQ_FR, hbmpc_)
 TYPED_PARTIES(uint64_t, REQ_GL, hbmpc_gl_)
+// ---- square roots, inverses, RandBit's phase 2 (kernels_sqrt.hpp) --------------------------------------------------
+// the context's constants: omega power tables, exponents, 2^-1, the subgroup look-up (tables_sqrt.hpp); one table per implementation
+static ShareErrorCode sqrt_tab(hbmpc_ctx* ctx, SqrtTab* t) {
+    const int impl = ctx->impl;
+    std::array<size_t, 5> aux = {0, 0, 0, 0, 0};
+    const uint32_t* p = nullptr;
+    ShareErrorCode rc;
+    try {
+        rc = get_table(ctx, key("sqrt", {}, impl), [&] {
+            SqrtLayout L;
+            std::vector<uint32_t> w;
+            if (impl == IMPL_GOLD) {
+                const uint64_t mod[4] = {HGl::P, 0, 0, 0};
+                w = build_sqrt_table<HGl>(mod, HGl::one(), impl, &L);
+            } else {
+                w = build_sqrt_table<HFr>(HFr::MOD, rdev_value(impl), impl, &L);
+            }
+            aux = {(size_t)L.kbits, (size_t)L.kshift, (size_t)L.bits_sqrt, (size_t)L.bits_inv, 0};
+            return w;
+        }, &p, &aux);
+    } catch (const std::exception& e) {
+        return fail(ctx, HBMPC_NO_DEVICE, e.what());
+    }
+    if (rc != ShareSuccess) return rc;
+    const SqrtLayout L = sqrt_layout(impl, (int)aux[0], (int)aux[1], (int)aux[2], (int)aux[3]);
+    t->negw = p + L.negw, t->posw = p + L.posw, t->r2 = p + L.r2, t->one_p = p + L.one_p, t->half = p + L.half, t->half_p = p + L.half_p;
+    t->e_sqrt = p + L.e_sqrt, t->e_inv = p + L.e_inv, t->keyt = reinterpret_cast<const uint8_t*>(p + L.keyt);
+    t->bits_sqrt = L.bits_sqrt, t->bits_inv = L.bits_inv;
+    t->kshift = (uint32_t)L.kshift, t->kmask = (1u << L.kbits) - 1;
+    return ShareSuccess;
+}
+static ShareErrorCode sqrt_inverse_any(hbmpc_ctx* ctx, bool inverse, const void* a, size_t N, void* out, uint8_t* flag, void* stream) {
+    ELEM_PROLOGUE
+    if (!a || !out || !flag) return fail(ctx, InvalidInput, "null buffer");
+    SqrtTab t;
+    const ShareErrorCode rc = sqrt_tab(ctx, &t);
+    if (rc != ShareSuccess) return rc;
+    if (inverse) launch_inverse(ctx->impl, W(a), N, t, WO(out), flag, s);
+    else launch_sqrt(ctx->impl, W(a), N, t, WO(out), flag, s);
+    HIP_TRY(ctx, hipGetLastError());
+    return ShareSuccess;
+}
+static ShareErrorCode randbit_finalize_any(hbmpc_ctx* ctx, const void* a, const void* sq, size_t N, size_t parties, void* out, uint8_t* status,
+                                           hbmpc_randbit_summary* summary, void* stream) {
+    if (!ctx) return InvalidInput;
+    if (!summary || (N && (!a || !sq || !out || !status))) return fail(ctx, InvalidInput, "null buffer");
+    CHECK_PARTIES(parties);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = pick(ctx, stream);
+    SqrtTab t;
+    const ShareErrorCode rc = sqrt_tab(ctx, &t);
+    if (rc != ShareSuccess) return rc;
+    static_assert(sizeof(hbmpc_randbit_summary) == sizeof(RandBitSummaryDev), "summary layout");
+    HIP_TRY(ctx, hipMemsetAsync(summary, 0xff, 8, s));  // first = all ones
+    HIP_TRY(ctx, hipMemsetAsync((char*)summary + 8, 0, 8, s));
+    if (N == 0) return ShareSuccess;
+    launch_randbit_finalize(ctx->impl, W(a), W(sq), N, (unsigned)parties, t, WO(out), status, reinterpret_cast<RandBitSummaryDev*>(summary), s);
+    HIP_TRY(ctx, hipGetLastError());
+    return ShareSuccess;
+}
+// host-pointer forms: inputs staged, the two outputs copied back
+static ShareErrorCode sqrt_inverse_host(hbmpc_ctx* ctx, bool inverse, const void* a, size_t N, void* out, uint8_t* flag) {
+    if (!ctx) return InvalidInput;
+    if (N == 0) return ShareSuccess;
+    if (!a || !out || !flag) return fail(ctx, InvalidInput, "null buffer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t eb = ebytes(ctx);
+    Stage st(ctx, 2 * N * eb + N, 3);
+    void *pa = nullptr, *po = nullptr, *pf = nullptr;
+    HIP_TRY(ctx, st.in(a, N * eb, &pa));
+    HIP_TRY(ctx, st.alloc(N * eb, &po));
+    HIP_TRY(ctx, st.alloc(N, &pf));
+    const ShareErrorCode rc = sqrt_inverse_any(ctx, inverse, pa, N, po, (uint8_t*)pf, nullptr);
+    if (rc != ShareSuccess) return rc;
+    HIP_TRY(ctx, st.out(out, po, N * eb));
+    HIP_TRY(ctx, st.out(flag, pf, N));
+    HIP_TRY(ctx, st.finish());
+    return ShareSuccess;
+}
+#define TYPED_SQRT(T, REQ, PFX)                                                                                                             \
+    extern "C" ShareErrorCode PFX##fr_sqrt(hbmpc_ctx* ctx, const T* a, size_t N, T* root_out, uint8_t* has_root_out) {                       \
+        REQ(ctx);                                                                                                                           \
+        return sqrt_inverse_host(ctx, false, a, N, root_out, has_root_out);                                                                 \
+    }                                                                                                                                       \
+    extern "C" ShareErrorCode PFX##dev_fr_sqrt(hbmpc_ctx* ctx, const T* a, size_t N, T* root_out, uint8_t* has_root_out, void* stream) {     \
+        REQ(ctx);                                                                                                                           \
+        return sqrt_inverse_any(ctx, false, a, N, root_out, has_root_out, stream);                                                          \
+    }                                                                                                                                       \
+    extern "C" ShareErrorCode PFX##fr_inverse(hbmpc_ctx* ctx, const T* a, size_t N, T* inv_out, uint8_t* ok_out) {                            \
+        REQ(ctx);                                                                                                                           \
+        return sqrt_inverse_host(ctx, true, a, N, inv_out, ok_out);                                                                         \
+    }                                                                                                                                       \
+    extern "C" ShareErrorCode PFX##dev_fr_inverse(hbmpc_ctx* ctx, const T* a, size_t N, T* inv_out, uint8_t* ok_out, void* stream) {         \
+        REQ(ctx);                                                                                                                           \
+        return sqrt_inverse_any(ctx, true, a, N, inv_out, ok_out, stream);                                                                  \
+    }                                                                                                                                       \
+    extern "C" ShareErrorCode PFX##dev_randbit_finalize_parties(hbmpc_ctx* ctx, const T* a, const T* opened_sq, size_t N, size_t parties,    \
+                                                                T* out, uint8_t* status_out, hbmpc_randbit_summary* summary_dev,            \
+                                                                void* stream) {                                                             \
+        REQ(ctx);                                                                                                                           \
+        return randbit_finalize_any(ctx, a, opened_sq, N, parties, out, status_out, summary_dev, stream);                                   \
+    }
+TYPED_SQRT(U256, REQ_FR, hbmpc_)
+TYPED_SQRT(uint64_t, REQ_GL, hbmpc_gl_)
+#undef TYPED_SQRT
 static ShareErrorCode truncpr_rdash_impl(hbmpc_ctx* ctx, const U256* r_bits, size_t m, size_t N, size_t parties, U256* r_dash,
                                          void* stream) {
     REQ_FR(ctx);

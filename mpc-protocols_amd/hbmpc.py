@@ -521,6 +521,36 @@ class Engine:
         return self._f("dev_beaver_open_shares_paired")(self.ctx, C.c_void_p(a_d), C.c_void_p(b_d), C.c_void_p(x_d), C.c_void_p(y_d),
                                                           C.c_size_t(N), C.c_size_t(parties), C.c_void_p(de_d), C.c_void_p(stream))
 
+    # ---- square roots, inverses, RandBit's phase 2 (csrc/kernels_sqrt.hpp) ----
+    def fr_sqrt(self, a):
+        """ark's Field::sqrt of every element: (rc, roots, has_root bytes); a root is 0 where ark returns None"""
+        a = np.ascontiguousarray(a)
+        N = a.shape[0]
+        root, ok = self._new((N,)), np.zeros(N, dtype=np.uint8)
+        rc = self._f("fr_sqrt")(self.ctx, _p(a), C.c_size_t(N), _p(root), _p(ok))
+        return rc, root, ok
+
+    def fr_inverse(self, a):
+        """Field::inverse of every element: (rc, inverses, ok bytes); zero has none (inverse 0, ok 0)"""
+        a = np.ascontiguousarray(a)
+        N = a.shape[0]
+        inv, ok = self._new((N,)), np.zeros(N, dtype=np.uint8)
+        rc = self._f("fr_inverse")(self.ctx, _p(a), C.c_size_t(N), _p(inv), _p(ok))
+        return rc, inv, ok
+
+    def dev_fr_sqrt(self, a_d, N, root_d, has_root_d, stream=0):
+        return self._f("dev_fr_sqrt")(self.ctx, C.c_void_p(a_d), C.c_size_t(N), C.c_void_p(root_d), C.c_void_p(has_root_d), C.c_void_p(stream))
+
+    def dev_fr_inverse(self, a_d, N, inv_d, ok_d, stream=0):
+        return self._f("dev_fr_inverse")(self.ctx, C.c_void_p(a_d), C.c_size_t(N), C.c_void_p(inv_d), C.c_void_p(ok_d), C.c_void_p(stream))
+
+    def randbit_finalize_parties(self, a_d, sq_d, N, parties, out_d, status_d, summary_d, stream=0):
+        """RandBit phase 2 for `parties` parties (hbmpc_[gl_]dev_randbit_finalize_parties; device pointers): a [parties][N], sq [N] the
+        opened squares -> out [parties][N], status [N] bytes (0 ok, 1 zero square, 2 no root), summary (16 bytes: u64 first =
+        (status << 32) | index, u32 n_failed); returns the ShareErrorCode"""
+        return self._f("dev_randbit_finalize_parties")(self.ctx, C.c_void_p(a_d), C.c_void_p(sq_d), C.c_size_t(N), C.c_size_t(parties),
+                                                         C.c_void_p(out_d), C.c_void_p(status_d), C.c_void_p(summary_d), C.c_void_p(stream))
+
     # ---- wire codec ----
     def dev_pack_fvec(self, rows_d, row_stride, G, n_rows, payloads_d, payload_stride_bytes, stream=0):
         return self.L.hbmpc_dev_pack_fvec(self.ctx, C.c_void_p(rows_d), C.c_size_t(row_stride), C.c_size_t(G),

@@ -12,6 +12,7 @@ in the library; this file only names things for the tests and bench.py.
   RanDouSha      DouShaNode::init_batch + RanDouShaNode::init_batch + reconstruction_handler + try_finalize
                  double_share/double_share_generation.rs:151-215, ran_dou_sha/mod.rs:371-449,569-602,314-331
   Preprocessing  run_preprocessing's triple part (honeybadger/mod.rs:1239-1393): RanSha -> a, b; RanDouSha -> r; TripleGen
+  RandBit        RandBit: Beaver square of a, BatchRecon of a^2, phase 2   fpmul/rand_bit.rs:242-293,197-220
 """
 from __future__ import annotations
 
@@ -228,3 +229,42 @@ class Preprocessing(_Pipe):
             bad, first = self._bad()
             if bad:
                 raise RuntimeError(f"Preprocessing: {bad} verifier checks failed (first: column {first})")
+
+
+class RandBit(_Pipe):
+    """N random bits for n parties from N shared values a and one Beaver triple (ta, tb, tc) each, over either field (N a
+    multiple of t + 1).  Buffers a, ta, tb, tc, out, sq are [party][N]; sqop [N] the opened squares; status [N] bytes and summary
+    (u64 first, u32 n_failed) the finalize's; rstatus_de / rstatus_sq and summary_de_first, summary_de, summary_sq_first,
+    summary_sq the four decodes'.  run(check=True) raises with HBMPC_ZERO_SQUARE (102) / HBMPC_NO_SQUARE_ROOT (103) where
+    phase 2's `?` returns, or with a failed open's error."""
+
+    ZERO_SQUARE, NO_SQUARE_ROOT = 102, 103
+
+    def __init__(self, eng, n, t, N, stream=0):
+        self.n, self.t, self.N = n, t, N
+        super().__init__(eng, self._create(eng, "hbmpc_pipe_randbit_create", n, t, N, stream=stream), stream)
+
+    def upload(self, a, ta, tb, tc):
+        for name, src in (("a", a), ("ta", ta), ("tb", tb), ("tc", tc)):
+            self.upload_named(name, src)
+
+    def download(self, which="out"):
+        shape = (self.N,) if which == "sqop" else (self.n, self.N)
+        return self.download_named(which, shape)
+
+    def bytes_of(self, name, nbytes):
+        """raw bytes of a named buffer (status bytes, summaries): hbmpc_pipe_download counts field elements"""
+        out = np.zeros(nbytes, dtype=np.uint8)
+        self.sync()
+        self._rc(self.eng.L.hbmpc_memcpy_d2h(self.eng.ctx, out.ctypes.data_as(C.c_void_p), C.c_void_p(self.buffer(name)[0]),
+                                             C.c_size_t(nbytes), C.c_void_p(self.stream)), f"bytes of {name!r}")
+        self.sync()
+        return out
+
+    def status(self):
+        return self.bytes_of("status", self.N)
+
+    def rb_summary(self):
+        """(first, n_failed) of the finalize"""
+        b = self.bytes_of("summary", 16)
+        return int(b[:8].view(np.uint64)[0]), int(b[8:12].view(np.uint32)[0])

@@ -30,6 +30,7 @@ use crate::common::share::ShareError; // mpc/src/common/share/mod.rs:12-27
 use crate::common::SecretSharingScheme; // mpc/src/common/mod.rs:101-128
 use crate::honeybadger::robust_interpolate::robust_interpolate::RobustShare; // robust_interpolate.rs:17-29
 use crate::honeybadger::robust_interpolate::InterpolateError; // robust_interpolate/mod.rs:7-27
+use crate::honeybadger::fpmul::RandBitError; // fpmul/mod.rs (the error type of fpmul/rand_bit.rs)
 
 // ---- Fr <-> U256: the conversion of mpc/src/ffi/c_bindings/mod.rs:37-49 -------------------------------------------
 #[inline]
@@ -283,6 +284,13 @@ impl GpuShares {
         let rc = unsafe { sys::hbmpc_pipe_preprocessing_create(self.ctx, n, t, triples, stream, &mut p) };
         self.wrap(rc, p, n)
     }
+    /// `RandBit` for all n parties: Beaver square of a, BatchRecon of a^2, phase 2 (fpmul/rand_bit.rs:242-293,197-220); `bits` a multiple
+    /// of t + 1 (rand_bit.rs:253-255); either field, as the context was created
+    pub fn pipe_randbit(&self, n: usize, t: usize, bits: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_randbit_create(self.ctx, n, t, bits, stream, &mut p) };
+        self.wrap(rc, p, n)
+    }
 }
 
 impl<'a> GpuPipeline<'a> {
@@ -329,6 +337,21 @@ impl<'a> GpuPipeline<'a> {
         self.gpu.check(rc, 0)?;
         let rc = unsafe { sys::hbmpc_pipe_run(self.pipe) };
         self.gpu.check(rc, 0)
+    }
+    /// checked run of a RandBit pipeline (`pipe_randbit`): phase 2's errors come back as the reference's variants
+    /// (rand_bit.rs:198-207); a failed open is `Abort`, as a failed BatchRecon ends the reference's session
+    pub fn randbit(&self) -> Result<(), RandBitError> {
+        let rc = unsafe { sys::hbmpc_pipe_set_checked(self.pipe, 1) };
+        if rc != sys::ShareSuccess {
+            return Err(RandBitError::Abort);
+        }
+        let rc = unsafe { sys::hbmpc_pipe_run(self.pipe) };
+        match rc {
+            sys::ShareSuccess => Ok(()),
+            sys::HBMPC_ZERO_SQUARE => Err(RandBitError::ZeroSquare),
+            sys::HBMPC_NO_SQUARE_ROOT => Err(RandBitError::SquareRoot),
+            _ => Err(RandBitError::Abort),
+        }
     }
     /// the two halves of a producer's run: the dealers' `compute_shares`, then everything after their messages have arrived
     pub fn deal(&self) -> Result<(), InterpolateError> {
