@@ -135,40 +135,53 @@ std::vector<uint32_t> build_gao_tables(hbmpc_ctx* ctx, const std::vector<std::ve
     return impl == IMPL_GOLD ? build_gao_tables_t<HGl>(*domain_inv<HGl>(ctx, n), known_sets, ks, alpha_ids, impl, lay)
                              : build_gao_tables_t<HFr>(*domain_inv<HFr>(ctx, n), known_sets, ks, alpha_ids, impl, lay);
 }
-// The matrix-core decode (kernels_mfma.hpp): verify rows and coefficient rows as int8 MFMA tiles.  Returns false when
-// the shape is outside what that path covers (the caller then launches the lane-per-chunk kernels).
-// pair (hbmpc_dev_fpmul_parties): the sender values are a - x | b - y formed after loading (MfmaRowsArgs::sub_x) -- only as ONE
-// launch of the tile-walking kernel; false otherwise, with nothing enqueued.
-bool try_mfma_recover(hbmpc_ctx* ctx, const SortedSenders& ss, const RecoverArgs& ra, size_t n, size_t d, size_t t, bool p0,
-                      hipStream_t s, ShareErrorCode* rc_out, bool* direct, const PairInput* pair = nullptr, int only_coeff = 0, int second_coeff = -1) {
-    // second_coeff >= 0: TWO outputs per chunk, coefficients only_coeff and second_coeff (chunk-major [G][2]; p0 is false then)
-    const size_t m = d + 1, needed = d + t + 1, nv = needed - m, ow = second_coeff >= 0 ? 2 : p0 ? 1 : m;
-    *rc_out = ShareSuccess;
-    if (ctx->impl != IMPL_U29 || !ctx->matrix_cores || ctx->force_generic) return false;
-    // a call without OEC rounds is one launch here, flat at 7 - 12 us from 512 to 16 384 chunks, while the wave-per-chunk
-    // kernel grows with the batch: ahead from ~2 000 chunks (tools/time_team_vs_wide.py); with OEC rounds (three more
-    // launches behind the decode) from ~4 000 (15 us against 18 us at 4 096 chunks of config 3, tools/sweep_recover.py)
-    if (m < 2 || m > MF_MAX_M) return false;
+// the hbmpc_ctx fields of the decode's rule (recover_route.hpp)
+RecoverKnobs recover_knobs(const hbmpc_ctx* ctx) {
+    return RecoverKnobs{ctx->impl, ctx->force_generic, ctx->matrix_cores, ctx->mfma_team, ctx->mfma_bfly, ctx->direct_fail, ctx->second_chance,
+                        ctx->list_rows_in_kernel, ctx->lazy_fallback_tables, ctx->wide_max_chunks, ctx->mfma_min_cached, ctx->mfma_min_direct,
+                        ctx->mfma_min_gold_direct, ctx->mfma_min_gold_oec, ctx->mfma_wgs, ctx->n_cus};
+}
+
+// One batch decode.  Its forms (group, second_coeff, only_coeff, pair) are those of RecoverShape (recover_route.hpp); a form that
+// does not cover the call answers HBMPC_NOT_FUSED with nothing enqueued, and the caller runs the separate launches.
+struct RecoverCall {
+    const size_t* sender_ids = nullptr;
+    size_t S = 0;
+    const void* evals = nullptr;   // unused by the pair form: its values are the differences of `pair`
+    size_t row_stride = 0;         // 0: G
+    size_t G = 0, n = 0, d = 0, t = 0;
+    void* out = nullptr;
+    uint32_t* ncoeffs = nullptr;
+    uint8_t* status = nullptr;
+    hbmpc_recover_summary* summary = nullptr;
+    bool p0 = false;
+    void* stream = nullptr;
+    const size_t* slots = nullptr;  // the caller's row i lives at evals + slots[i] * row_stride (rows in place at their senders' slots)
+    bool host_call = false;
+    const PairInput* pair = nullptr;
+    int only_coeff = 0, second_coeff = -1;
+    size_t group = 0, group_stride = 0;  // group q's values q * group_stride elements further on in every sender row (RecoverArgs::group)
+};
+
+// the decode's table of a sender set: the verify rows (vm), then the coefficient rows (bc)
+template <class H>
+ShareErrorCode rec_table(hbmpc_ctx* ctx, const DomainInv<H>& dom, const std::vector<size_t>& ids, size_t n, size_t d, size_t t, const uint32_t** out) {
+    return get_table(ctx, ids_key("rec", ids, d + t + 1, n, d, t, ctx->impl), [&] {
+        const RecoverTables T = build_recover_tables<H>(dom, ids, d, t, ctx->impl);
+        std::vector<uint32_t> both = T.vm;
+        both.insert(both.end(), T.bc.begin(), T.bc.end());
+        return both;
+    }, out);
+}
+
+// The matrix-core routes of plan_recover (MfmaRowsSub, MfmaRowsTeam, MfmaRows): the sender set's table, the arguments, the launch.
+// Returns false when the route does not run and nothing was enqueued (a capture would have to build the table, or the launcher
+// declines); true when it ran or *rc_out holds an error.
+bool run_mfma_recover(hbmpc_ctx* ctx, const RecoverRoute& r, const SortedSenders& ss, const RecoverArgs& ra, const RecoverCall& c, hipStream_t s,
+                      ShareErrorCode* rc_out) {
+    const size_t n = c.n, d = c.d, t = c.t, m = d + 1, needed = d + t + 1, nv = needed - m, ow = c.second_coeff >= 0 ? 2 : c.p0 ? 1 : m;
     const size_t rowb = mf_row_bytes(m);
-    // up to two tiles per workgroup: the workgroup-per-tile kernel (its LDS also holds 32 flag words).  Measured crossover
-    // (tools/time_team.py, profiles/r02_team_kernel.txt): ahead at 8 000 and 16 384 chunks for every shape, behind at 32 768
-    const int nwg = ctx->mfma_wgs ? ctx->mfma_wgs : ctx->n_cus;
-    const bool team = !pair && ctx->mfma_team && (ra.G + 31) / 32 <= (size_t)nwg * 2;
-    const int cap = (int)((160 * 1024 - (team ? 128 : 0)) / rowb);
-    if (pair && (!*direct || !p0 || pair->N % 32 != 0 || !mfma_sub_covers((int)m))) return false;
-    // lane offsets inside a row / inside the output are 32-bit
-    if (ra.G * 32 >= ((size_t)1 << 32) || ra.G * ow * 32 >= ((size_t)1 << 32)) return false;
-    mf::MfmaRowsArgs a;
-    memset(&a, 0, sizeof a);
-    if (!mf::mf_plan_roles((int)(nv + ow), (int)nv, cap, nwg, &a)) return false;
-    // the whole call in this launch (no OEC round): only when one role serves verify AND output rows -- with two, the
-    // role that writes the coefficients does not know the verdict and the call keeps its k_gao launch
-    const bool one_launch = *direct && a.nroles == 1;
-    if (pair && !one_launch) return false;
-    // the single-launch threshold applies to single-launch calls only (ADVICE r2: a two-role decode of 2048 .. 4095 chunks
-    // used to take this path below its measured crossover)
-    const size_t min_cached = one_launch ? std::min(ctx->mfma_min_cached, ctx->mfma_min_direct) : ctx->mfma_min_cached;
-    if (ra.G < min_cached) return false;
+    *rc_out = ShareSuccess;
     // The table of a sender set not seen before: its rows x m coefficients come from the host (tables.hpp: no field
     // inversion, ~0.05 ms for config 3), the 32 shifted digit copies of each -- 239 KB for config 3 -- are expanded on the
     // device (kernels_tables.hpp: two short launches on the context's stream).  Round 2 built all of it on the host
@@ -176,16 +189,16 @@ bool try_mfma_recover(hbmpc_ctx* ctx, const SortedSenders& ss, const RecoverArgs
     // every batch from the crossover on takes it.
     // only_coeff = k > 0 (a P(0)-shaped call that keeps coefficient k instead of coefficient 0): its own table, the verify rows
     // followed by coefficient row k
-    const bool sel = only_coeff > 0 || second_coeff >= 0;
-    const std::string tkey = ids_key(sel ? ("mfrec_k" + std::to_string(only_coeff) + "_" + std::to_string(second_coeff)).c_str() : "mfrec", ss.ids, needed, n, d, t,
-                                     ctx->impl);
+    const bool sel = c.only_coeff > 0 || c.second_coeff >= 0;
+    const std::string tkey = ids_key(sel ? ("mfrec_k" + std::to_string(c.only_coeff) + "_" + std::to_string(c.second_coeff)).c_str() : "mfrec", ss.ids,
+                                     needed, n, d, t, ctx->impl);
     const auto dom = domain_inv<HFr>(ctx, n);  // before the table calls: their builders run under the context's lock, which this takes too
     auto table_rows = [&] {
         std::vector<std::vector<HFr>> rows_all = recover_coeff_rows<HFr>(*dom, ss.ids, d, t);
         if (sel) {
             std::vector<std::vector<HFr>> picked(rows_all.begin(), rows_all.begin() + nv);
-            picked.push_back(rows_all[nv + only_coeff]);
-            if (second_coeff >= 0) picked.push_back(rows_all[nv + second_coeff]);
+            picked.push_back(rows_all[nv + c.only_coeff]);
+            if (c.second_coeff >= 0) picked.push_back(rows_all[nv + c.second_coeff]);
             return picked;
         }
         return rows_all;
@@ -210,6 +223,9 @@ bool try_mfma_recover(hbmpc_ctx* ctx, const SortedSenders& ss, const RecoverArgs
         *rc_out = get_table(ctx, tkey, [&] { return build_mfma_table(table_rows(), m); }, &tab);
     }
     if (*rc_out != ShareSuccess) return true;
+    mf::MfmaRowsArgs a;
+    memset(&a, 0, sizeof a);
+    mf::mf_take_plan(r.plan, &a);
     a.in = (const uint8_t*)ra.evals;
     a.G = ra.G;
     a.in_chunk_major = 0;
@@ -225,26 +241,21 @@ bool try_mfma_recover(hbmpc_ctx* ctx, const SortedSenders& ss, const RecoverArgs
     a.flagged = ra.flagged;
     a.counters = ra.counters;
     a.summary = ra.summary;
-    *direct = one_launch;
-    a.direct = *direct ? 1 : 0;
+    a.direct = r.one_launch ? 1 : 0;
     const int mi = (int)m;
-    if (pair) {
+    if (c.pair) {
+        const PairInput* pair = c.pair;
         a.in = (const uint8_t*)pair->a, a.sub_x = (const uint8_t*)pair->x, a.in2 = (const uint8_t*)pair->b, a.sub_x2 = (const uint8_t*)pair->y;
         a.sub_half = pair->N, a.row_stride = pair->N;
         return launch_mfma_rows_sub(mi, a, ctx->device, s);
     }
-    return launch_mfma_rows(mi, a, ctx->device, s, team);
+    return launch_mfma_rows(mi, a, ctx->device, s, r.team);
 }
 
-// The same over Goldilocks (kernels_mfma_gl.hpp): the table is a few KB and costs microseconds to build, every row of a call
-// fits one workgroup's LDS, so there is neither a sighting rule nor a role plan.
-bool try_mfma_recover_gl(hbmpc_ctx* ctx, const SortedSenders& ss, const RecoverArgs& ra, size_t n, size_t d, size_t t, bool p0,
-                         hipStream_t s, ShareErrorCode* rc_out, bool direct) {
-    const size_t m = d + 1, needed = d + t + 1, nv = needed - m, ow = p0 ? 1 : m;
-    *rc_out = ShareSuccess;
-    if (ctx->impl != IMPL_GOLD || !ctx->matrix_cores || ctx->force_generic) return false;
-    if (m < 2 || m > MFGL_MAX_M || ra.G < (direct ? ctx->mfma_min_gold_direct : ctx->mfma_min_gold_oec)) return false;
-    if (mfgl_table_bytes(nv + ow, m) + 2048 > 160 * 1024) return false;
+// the same over Goldilocks (MfmaRowsGl)
+bool run_mfma_recover_gl(hbmpc_ctx* ctx, const RecoverRoute& r, const SortedSenders& ss, const RecoverArgs& ra, const RecoverCall& c, hipStream_t s,
+                         ShareErrorCode* rc_out) {
+    const size_t n = c.n, d = c.d, t = c.t, m = d + 1, needed = d + t + 1, nv = needed - m, ow = c.p0 ? 1 : m;
     const auto domain_inv_gl = domain_inv<HGl>(ctx, n);
     const uint32_t* tab;
     *rc_out = get_table(ctx, ids_key("mfrecgl", ss.ids, needed, n, d, t, ctx->impl), [&] {
@@ -268,7 +279,7 @@ bool try_mfma_recover_gl(hbmpc_ctx* ctx, const SortedSenders& ss, const RecoverA
     a.flagged = ra.flagged;
     a.counters = ra.counters;
     a.summary = ra.summary;
-    a.direct = direct ? 1 : 0;
+    a.direct = r.one_launch ? 1 : 0;
     const size_t ntiles = (ra.G + 31) / 32;
     const unsigned grid = (unsigned)std::min<size_t>((ntiles + 3) / 4, (size_t)(ctx->mfma_wgs ? ctx->mfma_wgs : ctx->n_cus * 4));
     return launch_mfma_rows_gl(a, grid, ctx->device, s);
@@ -280,88 +291,71 @@ void launch_gao(int impl, const GaoArgs& ga, size_t n, unsigned grid, hipStream_
     else launch_gao_gold(ga, n, grid, s, inline_unscale);
 }
 
-ShareErrorCode batch_recover_dev(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const void* evals, size_t G,
-                                 size_t n, size_t d, size_t t, void* out, uint32_t* ncoeffs, uint8_t* status,
-                                 hbmpc_recover_summary* summary, bool p0, void* stream, size_t row_stride = 0,
-                                 const size_t* slots = nullptr, bool host_call = false, const PairInput* pair = nullptr, int only_coeff = 0,
-                                 int second_coeff = -1, size_t group = 0, size_t group_stride = 0) {
-    // group > 0: the G chunks are G / group groups of `group`, group q's values q * group_stride elements further on in every sender row
-    // (RecoverArgs::group).  Only as ONE launch of the wave-per-chunk kernel without OEC rounds: HBMPC_NOT_FUSED otherwise.
-    // second_coeff >= 0 (with p0 = false): the "do these S points lie on a polynomial of degree <= d" form -- t is S - d - 1 whatever n
-    // is (no Byzantine bound: every point beyond the first d + 1 is a verify row), and the two outputs per chunk are coefficients
-    // only_coeff and second_coeff (out [G][2]).  Wave-per-chunk or matrix-core kernels only: HBMPC_NOT_FUSED otherwise, nothing enqueued.
-    // only_coeff = k > 0: a P(0)-shaped call (p0 = true) whose one output per chunk is coefficient k (RanSha's exact-degree test needs
-    // the top coefficient alone, share_gen.rs:516-530).  Only for calls without OEC rounds (S == d + t + 1): the fallback kernels
-    // know P(0) only.
-    // pair: the senders' values are differences formed after loading by the matrix-core decode (kernels_mfma.hpp, SUB; `evals` is
-    // unused).  Only a P(0) call without OEC rounds that is ONE launch of that kernel can take the form: others return
-    // HBMPC_NOT_FUSED before anything is enqueued and the caller runs the separate launches.
-    if (row_stride == 0) row_stride = G;
-    if (ctx && row_stride < (group ? group : G)) return fail(ctx, InvalidInput, "row_stride must be >= G");
+// Which kernels a decode takes is decided in one place, recover_cover and plan_recover (recover_route.hpp); this validates, builds
+// the tables the chosen route needs, fills the kernel arguments and walks the plan.
+ShareErrorCode batch_recover_dev(hbmpc_ctx* ctx, RecoverCall c) {
+    if (c.row_stride == 0) c.row_stride = c.G;
+    const size_t S = c.S, G = c.G, n = c.n, d = c.d, t = c.t;
+    if (ctx && c.row_stride < (c.group ? c.group : G)) return fail(ctx, InvalidInput, "row_stride must be >= G");
     if (!ctx) return InvalidInput;
-    if (S && !sender_ids) return fail(ctx, InvalidInput, "null sender_ids");
-    if (group && (G % group != 0 || S != d + t + 1 || !ctx->direct_fail || G > ctx->wide_max_chunks || ctx->force_generic || slots || pair)) return HBMPC_NOT_FUSED;
+    if (S && !c.sender_ids) return fail(ctx, InvalidInput, "null sender_ids");
+    const RecoverKnobs k = recover_knobs(ctx);
+    RecoverShape sh{G, n, d, t, S};
+    sh.p0 = c.p0, sh.only_coeff = c.only_coeff, sh.second_coeff = c.second_coeff, sh.group = c.group;
+    sh.slots = c.slots != nullptr, sh.pair = c.pair != nullptr, sh.pair_N = c.pair ? c.pair->N : 0, sh.host_call = c.host_call;
+    if (recover_cover(k, sh, true) != RecoverCover::Run) return HBMPC_NOT_FUSED;
     SortedSenders ss;
-    ShareErrorCode rc = validate_senders(ctx, sender_ids, S, G, n, d, second_coeff >= 0 ? 0 : t, &ss);
+    ShareErrorCode rc = validate_senders(ctx, c.sender_ids, S, G, n, d, c.second_coeff >= 0 ? 0 : t, &ss);
     if (rc != ShareSuccess) return rc;
     if (n > 255) return fail(ctx, InvalidInput, "n > 255 (HoneyBadgerMPCNodeOpts limits n to 255)");
-    if (slots)
+    if (c.slots)
         for (size_t i = 0; i < S; ++i)
-            if (slots[i] > 255) return fail(ctx, InvalidInput, "row slot out of range (0..255)");
-    if ((!evals && !pair) || !out) return fail(ctx, InvalidInput, "null buffer");
+            if (c.slots[i] > 255) return fail(ctx, InvalidInput, "row slot out of range (0..255)");
+    if ((!c.evals && !c.pair) || !c.out) return fail(ctx, InvalidInput, "null buffer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = pick(ctx, stream);
+    hipStream_t s = pick(ctx, c.stream);
+    switch (recover_cover(k, sh, false)) {
+    case RecoverCover::NotFused: return HBMPC_NOT_FUSED;
+    case RecoverCover::SingleCoeffInvalid: return fail(ctx, InvalidInput, "a single coefficient: P(0)-shaped calls with exactly d + t + 1 senders, k <= d");
+    case RecoverCover::Run: break;
+    }
     const int impl = ctx->impl;
     const size_t m = d + 1, needed = d + t + 1;
-    if (second_coeff >= 0 &&
-        !(!p0 && S == needed && S > d && ctx->direct_fail && impl == IMPL_U29 && !ctx->force_generic && (size_t)second_coeff <= d && (size_t)only_coeff <= d &&
-          (G <= ctx->wide_max_chunks || ctx->matrix_cores)))
-        return HBMPC_NOT_FUSED;
-    if (only_coeff > 0 && second_coeff < 0 && !(p0 && S == needed && ctx->direct_fail && (size_t)only_coeff <= d)) return fail(ctx, InvalidInput, "a single coefficient: P(0)-shaped calls with exactly d + t + 1 senders, k <= d");
-    if (pair && !(S == needed && ctx->direct_fail && impl == IMPL_U29 && !ctx->force_generic && ctx->matrix_cores && p0 && pair->N % 32 == 0 && mfma_sub_covers((int)m)))
-        return HBMPC_NOT_FUSED;
 
     // --- tables (cached per sender set) ---
-    const uint32_t *vm_bc, *gao_dev;
-    RecoverTables T;
-    size_t vm_words = 0;
     const std::shared_ptr<const DomainInv<HFr>> dom_fr = impl == IMPL_GOLD ? nullptr : domain_inv<HFr>(ctx, n);
     const std::shared_ptr<const DomainInv<HGl>> dom_gl = impl == IMPL_GOLD ? domain_inv<HGl>(ctx, n) : nullptr;
-    rc = get_table(ctx, ids_key("rec", ss.ids, needed, n, d, t, impl), [&] {
-        T = impl == IMPL_GOLD ? build_recover_tables<HGl>(*dom_gl, ss.ids, d, t, impl) : build_recover_tables<HFr>(*dom_fr, ss.ids, d, t, impl);
-        std::vector<uint32_t> both = T.vm;
-        both.insert(both.end(), T.bc.begin(), T.bc.end());
-        return both;
-    }, &vm_bc);
+    const uint32_t* vm_bc;
+    rc = impl == IMPL_GOLD ? rec_table(ctx, *dom_gl, ss.ids, n, d, t, &vm_bc) : rec_table(ctx, *dom_fr, ss.ids, n, d, t, &vm_bc);
     if (rc != ShareSuccess) return rc;
-    vm_words = (needed - m) * m * impl_nl(impl);
+    const size_t vm_words = (needed - m) * m * impl_nl(impl);
     const uint32_t* sel2 = nullptr;  // second_coeff >= 0: [verify rows | row only_coeff | row second_coeff], contiguous
-    if (second_coeff >= 0) {
-        rc = get_table(ctx, ids_key(("rec_k" + std::to_string(only_coeff) + "_" + std::to_string(second_coeff)).c_str(), ss.ids, needed, n, d, t, impl), [&] {
+    if (c.second_coeff >= 0) {
+        rc = get_table(ctx, ids_key(("rec_k" + std::to_string(c.only_coeff) + "_" + std::to_string(c.second_coeff)).c_str(), ss.ids, needed, n, d, t, impl), [&] {
             const RecoverTables T2 = build_recover_tables<HFr>(*dom_fr, ss.ids, d, t, impl);
             const size_t rw = m * impl_nl(impl);
             std::vector<uint32_t> w = T2.vm;
-            w.insert(w.end(), T2.bc.begin() + only_coeff * rw, T2.bc.begin() + (only_coeff + 1) * rw);
-            w.insert(w.end(), T2.bc.begin() + second_coeff * rw, T2.bc.begin() + (second_coeff + 1) * rw);
+            w.insert(w.end(), T2.bc.begin() + c.only_coeff * rw, T2.bc.begin() + (c.only_coeff + 1) * rw);
+            w.insert(w.end(), T2.bc.begin() + c.second_coeff * rw, T2.bc.begin() + (c.second_coeff + 1) * rw);
             return w;
         }, &sel2);
         if (rc != ShareSuccess) return rc;
     }
+    const std::string gao_key = ids_key("gao", ss.ids, S, n, d, t, impl), sc_key = ids_key("sc", ss.ids, S, n, d, t, impl);
+    RecoverFacts facts;
+    facts.capturing = g_capturing > 0;
+    // (only a call with OEC rounds has fallback tables: the others skip the look-ups)
+    facts.fallback_cached = S > needed && table_cached(ctx, gao_key) && (!ctx->second_chance || table_cached(ctx, sc_key));
+    const RecoverPlan plan = plan_recover(k, sh, facts);
     GaoLayout lay;
     std::vector<std::vector<size_t>> known_sets;
     std::vector<int> ks;
-    for (size_t r = 1; r <= t; ++r) {  // oec_decode rounds (:589-593)
-        const size_t required = needed + r;
-        if (S < required) break;
-        known_sets.emplace_back(ss.ids.begin(), ss.ids.begin() + required);
+    for (size_t r = 1; r <= plan.rmax; ++r) {  // oec_decode rounds (:589-593)
+        known_sets.emplace_back(ss.ids.begin(), ss.ids.begin() + needed + r);
         ks.push_back((int)m);
     }
-    // second-chance tables (k_second_chance): only when at least one OEC round exists
-    const size_t rmax = S > needed ? std::min(t, S - needed) : 0;
-    const bool second = rmax >= 1 && ctx->second_chance;
-    const uint32_t* sc_dev = nullptr;
+    const uint32_t *gao_dev = nullptr, *sc_dev = nullptr;
     SecondTables sct;
-    const std::string gao_key = ids_key("gao", ss.ids, S, n, d, t, impl), sc_key = ids_key("sc", ss.ids, S, n, d, t, impl);
     auto fetch_fallback_tables = [&]() -> ShareErrorCode {
         // table and layout are one cache entry, published under one lock (two threads may decode the same new sender
         // set at once: the second finds either nothing or both)
@@ -379,200 +373,153 @@ ShareErrorCode batch_recover_dev(hbmpc_ctx* ctx, const size_t* sender_ids, size_
         lay.one_off = aux[2];
         lay.r2_off = aux[3];
         lay.exp_off = aux[4];
-        if (second) {
+        if (plan.second) {
             // the layout is a pure function of the shape: recompute it without the values when the table is cached
             frc = get_table(ctx, sc_key, [&] {
-                sct = impl == IMPL_GOLD ? build_second_tables<HGl>(*dom_gl, ss.ids, d, needed + rmax, impl)
-                                        : build_second_tables<HFr>(*dom_fr, ss.ids, d, needed + rmax, impl);
+                sct = impl == IMPL_GOLD ? build_second_tables<HGl>(*dom_gl, ss.ids, d, needed + plan.rmax, impl)
+                                        : build_second_tables<HFr>(*dom_fr, ss.ids, d, needed + plan.rmax, impl);
                 return sct.words;
             }, &sc_dev);
             if (frc != ShareSuccess) return frc;
-            sct.layout(m, needed + rmax, (size_t)impl_nl(impl));
+            sct.layout(m, needed + plan.rmax, (size_t)impl_nl(impl));
         }
         return ShareSuccess;
     };
-    // A NEW sender set with OEC rounds available: the Gao rounds' and the second-chance tables are host work (0.4 - 1.3 ms
-    // for n = 31 .. 64) that only chunks which fail the verification ever read.  They are built when the first kernel of
-    // the call has flagged a chunk -- one look at its counter, i.e. one stream synchronisation in a call that would
-    // otherwise have spent that time building -- and not at all while the senders are honest.  By default only for the
-    // host-pointer entry points (which synchronise anyway): a device-pointer call stays a pure enqueue, and a graph capture
-    // finds every table its eager warm-up run left behind (hbmpc_set_lazy_fallback_tables(ctx, 2) extends it to them).
-    const bool lazy = (ctx->lazy_fallback_tables == 2 || (ctx->lazy_fallback_tables == 1 && host_call)) && !g_capturing && !known_sets.empty() &&
-                      !(table_cached(ctx, gao_key) && (!second || table_cached(ctx, sc_key)));
     lay.n_rounds = (int)known_sets.size();
-    if (!lazy) {
+    if (!plan.lazy) {
         rc = fetch_fallback_tables();
         if (rc != ShareSuccess) return rc;
     }
 
     // --- scratch: [0, 64) counters + local summary | two flagged lists (G u32 each) | scales ---
-    // Two threads may drive one context (and so one stream): the kernels of a call must reach the stream as one
-    // uninterrupted sequence (they share the counters and lists of the stream's scratch).
-    std::lock_guard<std::mutex> enqueue_lock(ctx->enqueue_mu);
-    void* scratch;
-    const size_t scale_words = (size_t)impl_nl(ctx->impl) + 1;  // per flagged chunk: pending flag + l^N
-    bool dirty = false;
-    rc = get_scratch(ctx, s, 2048 + 2 * G * 4 + G * scale_words * 4, &scratch, &dirty);
-    if (rc != ShareSuccess) return rc;
-    uint32_t* counters = (uint32_t*)scratch;
-    uint32_t* flagged_list = counters + 512;
-    uint32_t* flagged_list2 = flagged_list + G;  // what the second-chance kernel leaves for OEC/Gao
-    uint32_t* scales = flagged_list2 + G;
-    uint32_t* summ = summary ? (uint32_t*)summary : counters + 4;
-    // There is no init launch: the row permutation travels in the ARGUMENTS of every kernel, the first kernel
-    // initialises the summary, and the counters are zero because the last kernel of the previous call on this stream
-    // left them so (k_unscale).  Fresh scratch, or a call that failed between its first and last launch, is the
-    // exception: then they are cleared here.
-    // A graph capture records the clear under the same condition (as a node it costs ~4 us per decode and replay, more than
-    // a small decode itself): a replay finds the counters at zero because whatever ran before it on the stream left them so,
-    // and hbmpc_graph_launch clears them itself when a call has failed since (the scratch is then marked dirty).
-    if (dirty) HIP_TRY(ctx, hipMemsetAsync(counters, 0, 128, s));  // counters[0..4), the local summary, the sub-tickets of finish_direct
-    set_scratch_dirty(ctx, s, true);
-    RowsArg rows_arg;
-    memset(&rows_arg, 0, sizeof rows_arg);
-    // slots: the caller's row i lives at evals + slots[i] * row_stride (rows in place at their senders' slots)
-    for (size_t i = 0; i < S; ++i) rows_arg.set(i, (unsigned)(pair ? ss.ids[i] : slots ? slots[ss.rows[i]] : ss.rows[i]));
-    RecoverArgs ra;
-    ra.evals = (const uint32_t*)evals;
-    ra.G = G;
-    ra.row_stride = row_stride;
-    ra.rows = rows_arg;
-    ra.needed = (int)needed;
-    ra.m = (int)m;
-    ra.vm = vm_bc;
-    ra.bc = vm_bc + vm_words + (size_t)only_coeff * m * impl_nl(impl);  // the P(0)-only kernels read one coefficient row: row 0, or row k
-    if (sel2) ra.vm = sel2, ra.bc = sel2 + vm_words;
-    ra.out = (uint32_t*)out;
-    ra.ncoeffs = ncoeffs;
-    ra.status = status;
-    ra.flagged = flagged_list;
-    ra.counters = counters;
-    ra.summary = summ;
-    ra.group = group, ra.group_stride = group_stride;
-    const unsigned grid = (unsigned)((G + 255) / 256);
-    SecondArgs sa;
-    if (second) {
-        sa.evals = (const uint32_t*)evals;
-        sa.G = G;
-        sa.row_stride = row_stride;
-        sa.rows = rows_arg;
-        sa.m = (int)m;
-        sa.P = (int)(needed + rmax);
-        sa.rmax = (int)rmax;
-        sa.out_width = p0 ? 1 : (int)m;
-        sa.flagged = flagged_list;
-        sa.flagged2 = flagged_list2;
-        sa.counters = counters;
-        sa.out = (uint32_t*)out;
-        sa.ncoeffs = ncoeffs;
-        sa.status = status;
-        sa.summary = summ;
-    }
-    auto second_tables_into_args = [&] {
-        if (!second) return;
-        sa.n_windows = sct.n_windows;
-        for (int w = 0; w < SECOND_MAX_WINDOWS; ++w) {
-            sa.win_start[w] = sct.win_start[w];
-            sa.ev[w] = sc_dev + sct.ev_off[w];
-            sa.bc[w] = sc_dev + sct.bc_off[w];
+    const size_t scale_words = (size_t)impl_nl(impl) + 1;  // per flagged chunk: pending flag + l^N
+    return with_decode_counters(ctx, s, 2048 + 2 * G * 4 + G * scale_words * 4, [&](uint32_t* counters) -> ShareErrorCode {
+        uint32_t* flagged_list = counters + 512;
+        uint32_t* flagged_list2 = flagged_list + G;  // what the second-chance kernel leaves for OEC/Gao
+        uint32_t* scales = flagged_list2 + G;
+        uint32_t* summ = c.summary ? (uint32_t*)c.summary : counters + 4;
+        // There is no init launch: the row permutation travels in the ARGUMENTS of every kernel, and the first kernel
+        // initialises the summary.
+        RowsArg rows_arg;
+        memset(&rows_arg, 0, sizeof rows_arg);
+        for (size_t i = 0; i < S; ++i) rows_arg.set(i, (unsigned)(c.pair ? ss.ids[i] : c.slots ? c.slots[ss.rows[i]] : ss.rows[i]));
+        RecoverArgs ra;
+        ra.evals = (const uint32_t*)c.evals;
+        ra.G = G;
+        ra.row_stride = c.row_stride;
+        ra.rows = rows_arg;
+        ra.needed = (int)needed;
+        ra.m = (int)m;
+        ra.vm = vm_bc;
+        ra.bc = vm_bc + vm_words + (size_t)c.only_coeff * m * impl_nl(impl);  // the P(0)-only kernels read one coefficient row: row 0, or row k
+        if (sel2) ra.vm = sel2, ra.bc = sel2 + vm_words;
+        ra.out = (uint32_t*)c.out;
+        ra.ncoeffs = c.ncoeffs;
+        ra.status = c.status;
+        ra.flagged = flagged_list;
+        ra.counters = counters;
+        ra.summary = summ;
+        ra.group = c.group, ra.group_stride = c.group_stride;
+        const unsigned grid = (unsigned)((G + 255) / 256);
+        SecondArgs sa;
+        if (plan.second) {
+            sa.evals = (const uint32_t*)c.evals;
+            sa.G = G;
+            sa.row_stride = c.row_stride;
+            sa.rows = rows_arg;
+            sa.m = (int)m;
+            sa.P = (int)(needed + plan.rmax);
+            sa.rmax = (int)plan.rmax;
+            sa.out_width = c.p0 ? 1 : (int)m;
+            sa.flagged = flagged_list;
+            sa.flagged2 = flagged_list2;
+            sa.counters = counters;
+            sa.out = (uint32_t*)c.out;
+            sa.ncoeffs = c.ncoeffs;
+            sa.status = c.status;
+            sa.summary = summ;
         }
-    };
-    if (!lazy) second_tables_into_args();
-    bool hit = false, second_done = false;
-    // S == d + t + 1 (what BatchRecon passes): no OEC round exists, a chunk that fails the verification fails for good,
-    // and the first kernel writes that itself -- ONE launch per decode (kernels_recover.hpp, fail_chunk / finish_direct)
-    bool direct = lay.n_rounds == 0 && !second && ctx->direct_fail;
-    ra.direct = direct ? 1 : 0;
-    // the matrix cores overtake the wave-per-chunk kernels at ~4 000 chunks (a call costs ~15 us whatever the batch: the
-    // workgroup-per-tile kernel and three launches on empty lists), the lane-per-chunk kernels from the start (tools/sweep_recover.py)
-    const bool consider_mfma = G > ctx->wide_max_chunks || G >= ctx->mfma_min_cached || (direct && G >= ctx->mfma_min_direct);
-    bool mf_direct = direct;
-    if (pair) {  // direct by the check at the top: S == needed leaves no OEC round and no second-chance window
-        if (!try_mfma_recover(ctx, ss, ra, n, d, t, p0, s, &rc, &mf_direct, pair)) return HBMPC_NOT_FUSED;  // nothing was enqueued (the counters' clear is harmless)
-        if (rc != ShareSuccess) return rc;
-        hit = true;
-    } else if (impl == IMPL_GOLD && only_coeff == 0 && !group && try_mfma_recover_gl(ctx, ss, ra, n, d, t, p0, s, &rc, direct)) {
-        if (rc != ShareSuccess) return rc;
-        hit = true;
-    } else if (!group && (consider_mfma || (second_coeff >= 0 && G > ctx->wide_max_chunks)) &&
-               try_mfma_recover(ctx, ss, ra, n, d, t, p0, s, &rc, &mf_direct, nullptr, only_coeff, second_coeff)) {
-        direct = mf_direct;
-        // chunks that fail the verification keep whatever the coefficient rows produced until the fallback kernels
-        // below rewrite them (accepted candidate, decoded polynomial, or zeros)
-        if (rc != ShareSuccess) return rc;
-        hit = true;
-    } else if (G <= ctx->wide_max_chunks && !ctx->force_generic) {
-        // small batch: a wave per chunk; a chunk that fails the verification tries the second-chance candidates in the
-        // same kernel (one launch less) when the windows fit a wave
-        const bool fuse = second && !lazy && needed + rmax - m <= 64 && m <= 64;
-        launch_recover_wide(impl, p0, ra, fuse ? &sa : nullptr, s, second_coeff >= 0 ? 2 : 0);
-        second_done = fuse;
-        hit = true;
-    } else if (second_coeff >= 0) {
-        return HBMPC_NOT_FUSED;  // no other kernel family writes two selected coefficients (nothing was enqueued)
-    } else if (impl == IMPL_U29 && m <= 16 && !ctx->force_generic)
-        hit = launch_recover((int)m, p0, ra, grid, s);
-    else if (impl == IMPL_GOLD && m <= 16 && !ctx->force_generic)
-        hit = launch_gold_recover((int)m, p0, ra, grid, s);
-    if (!hit) launch_recover_generic(impl, p0, ra, grid, s);
-    HIP_TRY(ctx, hipGetLastError());
+        auto second_tables_into_args = [&] {
+            if (!plan.second) return;
+            sa.n_windows = sct.n_windows;
+            for (int w = 0; w < SECOND_MAX_WINDOWS; ++w) {
+                sa.win_start[w] = sct.win_start[w];
+                sa.ev[w] = sc_dev + sct.ev_off[w];
+                sa.bc[w] = sc_dev + sct.bc_off[w];
+            }
+        };
+        if (!plan.lazy) second_tables_into_args();
 
-    if (direct) {
-        set_scratch_dirty(ctx, s, false);  // the kernel's last block left the counters at zero
-        return ShareSuccess;
-    }
-    if (lazy) {
-        uint32_t n_flagged = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&n_flagged, counters, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-        if (n_flagged == 0) {
+        // the first kernel: the candidates of plan_recover in order, the first that runs does the call
+        const RecoverRoute* ran = nullptr;
+        for (int i = 0; i < plan.count && !ran; ++i) {
+            const RecoverRoute& r = plan.route[i];
+            ra.direct = r.one_launch ? 1 : 0;
+            bool hit = true;
+            switch (r.kernel) {
+            case RecoverKernel::MfmaRowsSub:
+            case RecoverKernel::MfmaRowsTeam:
+            case RecoverKernel::MfmaRows: hit = run_mfma_recover(ctx, r, ss, ra, c, s, &rc); break;
+            case RecoverKernel::MfmaRowsGl: hit = run_mfma_recover_gl(ctx, r, ss, ra, c, s, &rc); break;
+            case RecoverKernel::Wide: launch_recover_wide(impl, c.p0, ra, r.second_in_kernel ? &sa : nullptr, s, r.ow_sel); break;
+            case RecoverKernel::RecoverM: hit = launch_recover((int)m, c.p0, ra, grid, s); break;
+            case RecoverKernel::GoldRecoverM: hit = launch_gold_recover((int)m, c.p0, ra, grid, s); break;
+            case RecoverKernel::Generic: launch_recover_generic(impl, c.p0, ra, grid, s); break;
+            }
+            if (rc != ShareSuccess) return rc;
+            if (hit) ran = &r;
+        }
+        if (!ran) return HBMPC_NOT_FUSED;  // the pair and select-two forms: nothing was enqueued (the counters' clear is harmless)
+        HIP_TRY(ctx, hipGetLastError());
+        if (ran->one_launch) return ShareSuccess;  // the kernel's last block left the counters at zero
+
+        // --- the tail ---
+        if (plan.lazy) {
+            uint32_t n_flagged = 0;
+            HIP_TRY(ctx, hipMemcpyAsync(&n_flagged, counters, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipStreamSynchronize(s));
             // nothing for the fallback kernels to do: the summary is as the first kernel initialised it (no fallback, no
             // failure) and the counters never left zero -- exactly what their launches on empty lists would leave
-            set_scratch_dirty(ctx, s, false);
-            return ShareSuccess;
+            if (n_flagged == 0) return ShareSuccess;
+            rc = fetch_fallback_tables();
+            if (rc != ShareSuccess) return rc;
+            second_tables_into_args();
         }
-        rc = fetch_fallback_tables();
-        if (rc != ShareSuccess) return rc;
-        second_tables_into_args();
-    }
-    if (second && !second_done) {
-        // grid-stride over the flagged list
-        if (!(impl == IMPL_U29 && !ctx->force_generic && launch_second_chance_m((int)m, sa, std::min(grid, 1024u), s)))
-            launch_second_chance(impl, sa, std::min(grid, 1024u), s);
+        if (plan.second && !ran->second_in_kernel) {
+            // grid-stride over the flagged list
+            if (!(plan.second_kernel == SecondKernel::M && launch_second_chance_m((int)m, sa, std::min(grid, 1024u), s)))
+                launch_second_chance(impl, sa, std::min(grid, 1024u), s);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        GaoArgs ga;
+        ga.evals = (const uint32_t*)c.evals;
+        ga.G = G;
+        ga.row_stride = c.row_stride;
+        ga.rows = rows_arg;
+        ga.reset = counters;
+        ga.alpha_s = gao_dev + lay.alpha_off;
+        ga.rounds = (const GaoRound*)gao_dev;
+        ga.n_rounds = lay.n_rounds;
+        ga.tables = gao_dev;
+        ga.k = (int)m;
+        ga.accept_min = (int)needed;
+        ga.out_width = c.p0 ? 1 : (int)m;
+        ga.flagged = plan.second ? flagged_list2 : flagged_list;
+        ga.counters = plan.second ? counters + 1 : counters;
+        ga.out = (uint32_t*)c.out;
+        ga.ncoeffs = c.ncoeffs;
+        ga.status = c.status;
+        ga.summary = summ;
+        ga.one_plain = gao_dev + lay.one_off;
+        ga.r2 = gao_dev + lay.r2_off;
+        ga.inv_exp = gao_dev + lay.exp_off;
+        ga.scales = scales;
+        // blocks stride over the flagged list; more blocks than resident slots just exit (3 waves/SIMD of 64..256 lanes)
+        const unsigned ggrid = (unsigned)std::min<size_t>(G, 2048);
+        launch_gao(impl, ga, n, ggrid, s, plan.gao_inline);
         HIP_TRY(ctx, hipGetLastError());
-    }
-    GaoArgs ga;
-    ga.evals = (const uint32_t*)evals;
-    ga.G = G;
-    ga.row_stride = row_stride;
-    ga.rows = rows_arg;
-    ga.reset = counters;
-    ga.alpha_s = gao_dev + lay.alpha_off;
-    ga.rounds = (const GaoRound*)gao_dev;
-    ga.n_rounds = lay.n_rounds;
-    ga.tables = gao_dev;
-    ga.k = (int)m;
-    ga.accept_min = (int)needed;
-    ga.out_width = p0 ? 1 : (int)m;
-    ga.flagged = second ? flagged_list2 : flagged_list;
-    ga.counters = second ? counters + 1 : counters;
-    ga.out = (uint32_t*)out;
-    ga.ncoeffs = ncoeffs;
-    ga.status = status;
-    ga.summary = summ;
-    ga.one_plain = gao_dev + lay.one_off;
-    ga.r2 = gao_dev + lay.r2_off;
-    ga.inv_exp = gao_dev + lay.exp_off;
-    ga.scales = scales;
-    // blocks stride over the flagged list; more blocks than resident slots just exit (3 waves/SIMD of 64..256 lanes)
-    const unsigned ggrid = (unsigned)std::min<size_t>(G, 2048);
-    // small batch: OEC/Gao un-scales its own results and is the last kernel of the call (no k_unscale launch).  The same
-    // when the call has no OEC round at all (S == d + t + 1, what BatchRecon passes: it decodes as soon as that many
-    // senders have arrived, batch_recon.rs:371-389): a flagged chunk can only fail, there is nothing to un-scale
-    launch_gao(impl, ga, n, ggrid, s, (G <= ctx->wide_max_chunks && !ctx->force_generic) || lay.n_rounds == 0);
-    HIP_TRY(ctx, hipGetLastError());
-    set_scratch_dirty(ctx, s, false);  // the whole sequence is on the stream: its last kernel leaves the counters at zero
-    return ShareSuccess;
+        return ShareSuccess;  // the whole sequence is on the stream: its last kernel leaves the counters at zero
+    });
 }
 
 ShareErrorCode batch_recover_host(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const void* evals, size_t G,
@@ -593,7 +540,8 @@ ShareErrorCode batch_recover_host(hbmpc_ctx* ctx, const size_t* sender_ids, size
     HIP_TRY(ctx, stg.alloc(G, &dst));
     // no device summary on this path: the status bytes come home anyway and say the same (and which failure is
     // reported no longer depends on which failing chunk finished last)
-    rc = batch_recover_dev(ctx, sender_ids, S, de, G, n, d, t, dout, (uint32_t*)dn, (uint8_t*)dst, nullptr, p0, nullptr, 0, nullptr, true);
+    rc = batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .evals = de, .G = G, .n = n, .d = d, .t = t, .out = dout, .ncoeffs = (uint32_t*)dn,
+                                 .status = (uint8_t*)dst, .p0 = p0, .host_call = true});
     if (rc != ShareSuccess) return rc;
     std::vector<uint8_t> st_local;
     if (!status) {
@@ -620,24 +568,27 @@ ShareErrorCode batch_recover_host(hbmpc_ctx* ctx, const size_t* sender_ids, size
                                                      uint32_t* ncoeffs_out_dev, uint8_t* status_out_dev,                  \
                                                      hbmpc_recover_summary* summary_dev, void* stream) {                  \
         REQ(ctx);                                                                                                         \
-        return batch_recover_dev(ctx, sender_ids, S, evals_dev, G, n, d, t, coeffs_out_dev, ncoeffs_out_dev,              \
-                                 status_out_dev, summary_dev, false, stream);                                             \
+        return batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .evals = evals_dev, .G = G, .n = n, .d = d, .t = t,    \
+                                       .out = coeffs_out_dev, .ncoeffs = ncoeffs_out_dev, .status = status_out_dev,         \
+                                       .summary = summary_dev, .stream = stream});                                          \
     }                                                                                                                     \
     extern "C" ShareErrorCode PFX##dev_batch_recover_p0(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S,               \
                                                         const T* evals_dev, size_t G, size_t n, size_t d, size_t t,       \
                                                         T* secrets_out_dev, uint8_t* status_out_dev,                      \
                                                         hbmpc_recover_summary* summary_dev, void* stream) {               \
         REQ(ctx);                                                                                                         \
-        return batch_recover_dev(ctx, sender_ids, S, evals_dev, G, n, d, t, secrets_out_dev, nullptr, status_out_dev,     \
-                                 summary_dev, true, stream);                                                              \
+        return batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .evals = evals_dev, .G = G, .n = n, .d = d, .t = t,    \
+                                       .out = secrets_out_dev, .status = status_out_dev, .summary = summary_dev, .p0 = true, \
+                                       .stream = stream});                                                                  \
     }                                                                                                                     \
     extern "C" ShareErrorCode PFX##dev_batch_recover_strided(                                                             \
         hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const T* evals_dev, size_t row_stride, size_t G, size_t n,    \
         size_t d, size_t t, int p0_only, T* out_dev, uint32_t* ncoeffs_out_dev, uint8_t* status_out_dev,                  \
         hbmpc_recover_summary* summary_dev, void* stream) {                                                               \
         REQ(ctx);                                                                                                         \
-        return batch_recover_dev(ctx, sender_ids, S, evals_dev, G, n, d, t, out_dev, p0_only ? nullptr : ncoeffs_out_dev, \
-                                 status_out_dev, summary_dev, p0_only != 0, stream, row_stride);                          \
+        return batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .evals = evals_dev, .row_stride = row_stride, .G = G, \
+                                       .n = n, .d = d, .t = t, .out = out_dev, .ncoeffs = p0_only ? nullptr : ncoeffs_out_dev, \
+                                       .status = status_out_dev, .summary = summary_dev, .p0 = p0_only != 0, .stream = stream}); \
     }                                                                                                                     \
     extern "C" ShareErrorCode PFX##dev_batch_recover_coeff_strided(                                                       \
         hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const T* evals_dev, size_t row_stride, size_t G, size_t n,    \
@@ -645,8 +596,9 @@ ShareErrorCode batch_recover_host(hbmpc_ctx* ctx, const size_t* sender_ids, size
         void* stream) {                                                                                                   \
         REQ(ctx);                                                                                                         \
         if (ctx && k > d) return fail(ctx, InvalidInput, "k must be <= d");                                               \
-        return batch_recover_dev(ctx, sender_ids, S, evals_dev, G, n, d, t, out_dev, nullptr, status_out_dev, summary_dev, \
-                                 true, stream, row_stride, nullptr, false, nullptr, (int)k);                              \
+        return batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .evals = evals_dev, .row_stride = row_stride, .G = G, \
+                                       .n = n, .d = d, .t = t, .out = out_dev, .status = status_out_dev, .summary = summary_dev, \
+                                       .p0 = true, .stream = stream, .only_coeff = (int)k});                                \
     }                                                                                                                     \
     extern "C" ShareErrorCode PFX##dev_recover_check_degree_strided(                                                      \
         hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const T* evals_dev, size_t row_stride, size_t G, size_t n,    \
@@ -660,9 +612,10 @@ ShareErrorCode batch_recover_host(hbmpc_ctx* ctx, const size_t* sender_ids, size
             if (top_only) {                                                                                               \
                 /* groups that follow each other inside the sender rows (group_stride == G) are one plain call of groups * G chunks */ \
                 const bool dense = group_stride == G;                                                                     \
-                const ShareErrorCode rc = batch_recover_dev(ctx, sender_ids, S, evals_dev, groups * G, n, t, t, ws_dev, nullptr, \
-                                                            status_out_dev, summary_dev, true, stream, row_stride, nullptr,   \
-                                                            false, nullptr, (int)t, -1, dense ? 0 : G, dense ? 0 : group_stride); \
+                const ShareErrorCode rc = batch_recover_dev(                                                              \
+                    ctx, {.sender_ids = sender_ids, .S = S, .evals = evals_dev, .row_stride = row_stride, .G = groups * G, .n = n, \
+                          .d = t, .t = t, .out = ws_dev, .status = status_out_dev, .summary = summary_dev, .p0 = true,     \
+                          .stream = stream, .only_coeff = (int)t, .group = dense ? 0 : G, .group_stride = dense ? 0 : group_stride}); \
                 if (rc == ShareSuccess) return check_top_coeff_any(ctx, ws_dev, status_out_dev, groups * G, t, bad_dev, stream, G); \
                 if (rc != HBMPC_NOT_FUSED) return rc;                                                                     \
             }                                                                                                             \
@@ -675,13 +628,15 @@ ShareErrorCode batch_recover_host(hbmpc_ctx* ctx, const size_t* sender_ids, size
             return ShareSuccess;                                                                                          \
         }                                                                                                                 \
         if (top_only) {                                                                                                   \
-            ShareErrorCode rc = batch_recover_dev(ctx, sender_ids, S, evals_dev, G, n, t, t, ws_dev, nullptr, status_out_dev, \
-                                                  summary_dev, true, stream, row_stride, nullptr, false, nullptr, (int)t);   \
+            ShareErrorCode rc = batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .evals = evals_dev, .row_stride = row_stride, \
+                                                        .G = G, .n = n, .d = t, .t = t, .out = ws_dev, .status = status_out_dev, \
+                                                        .summary = summary_dev, .p0 = true, .stream = stream, .only_coeff = (int)t}); \
             if (rc != ShareSuccess) return rc;                                                                            \
             return hbmpc_dev_check_top_coeff(ctx, ws_dev, status_out_dev, G, t, bad_dev, stream);                         \
         }                                                                                                                 \
-        ShareErrorCode rc = batch_recover_dev(ctx, sender_ids, S, evals_dev, G, n, t, t, ws_dev, nullptr, status_out_dev,   \
-                                              summary_dev, false, stream, row_stride);                                      \
+        ShareErrorCode rc = batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .evals = evals_dev, .row_stride = row_stride, \
+                                                    .G = G, .n = n, .d = t, .t = t, .out = ws_dev, .status = status_out_dev,     \
+                                                    .summary = summary_dev, .stream = stream});                                 \
         if (rc != ShareSuccess) return rc;                                                                                \
         return hbmpc_dev_check_degree(ctx, ws_dev, status_out_dev, G, t + 1, t, bad_dev, stream);                         \
     }                                                                                                                     \
@@ -691,8 +646,10 @@ ShareErrorCode batch_recover_host(hbmpc_ctx* ctx, const size_t* sender_ids, size
         uint8_t* status_out_dev, hbmpc_recover_summary* summary_dev, void* stream) {                                      \
         REQ(ctx);                                                                                                         \
         if (ctx && S && !row_slots) return fail(ctx, InvalidInput, "null row_slots");                                     \
-        return batch_recover_dev(ctx, sender_ids, S, evals_dev, G, n, d, t, out_dev, p0_only ? nullptr : ncoeffs_out_dev, \
-                                 status_out_dev, summary_dev, p0_only != 0, stream, row_stride, row_slots);               \
+        return batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .evals = evals_dev, .row_stride = row_stride, .G = G, \
+                                       .n = n, .d = d, .t = t, .out = out_dev, .ncoeffs = p0_only ? nullptr : ncoeffs_out_dev, \
+                                       .status = status_out_dev, .summary = summary_dev, .p0 = p0_only != 0, .stream = stream, \
+                                       .slots = row_slots});                                                                \
     }                                                                                                                     \
     extern "C" ShareErrorCode PFX##batch_recover(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const T* evals,      \
                                                  size_t G, size_t n, size_t d, size_t t, T* coeffs_out,                   \
@@ -721,63 +678,51 @@ static ShareErrorCode batch_interpolate_dev(hbmpc_ctx* ctx, const size_t* ids, s
     if (!ids || !evals_dev || !coeffs_out_dev) return fail(ctx, InvalidInput, "null buffer");
     ShareErrorCode rc = ShareSuccess;
     bool done = false, degree_in_kernel = false;
-    // All n parties of a full power-of-two domain (the RanDouSha verifier: n = 16 shares of each sharing): the interpolation
-    // is the inverse DFT, c_i = (1/n) sum_k y_k omega^(-i k), whose rows i and i + n/2 differ by the sign of the odd columns
-    // -- the point-pair matrix-core kernel with the inverse rows as its table (kernels_mfma_bfly.hpp), the shares read from
-    // their sender rows in place, the coefficients written chunk-major.  0.16 ms per 699 050 columns against 0.60 of the
-    // lane kernel (profiles/r03_producers.txt).
-    if (ctx->impl == IMPL_U29 && ctx->matrix_cores && ctx->mfma_bfly && !ctx->force_generic && S == n && n == domain_size(n) && n >= 8 &&
-        n <= MF_BFLY_MAX_M && (G + 31) / 32 > (size_t)(ctx->mfma_wgs ? ctx->mfma_wgs : ctx->n_cus) * 2 && G * n * 32 < ((size_t)1 << 32) &&
-        (row_stride == 0 || row_stride >= G)) {
+    const InterpPlan plan = plan_interpolate(recover_knobs(ctx), G, n, S, row_stride, degree_out_dev != nullptr, c0_out_dev != nullptr);
+    if (plan.route[0] != InterpKernel::Decode) {  // the inverse DFT on point pairs (recover_route.hpp)
         SortedSenders ss;
         rc = validate_senders(ctx, ids, S, G, n, S - 1, 0, &ss);
         if (rc != ShareSuccess) return rc;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         hipStream_t s = pick(ctx, stream);
         const size_t half = n / 2;
-        mf::MfmaRowsArgs a;
-        memset(&a, 0, sizeof a);
-        if (mf::mf_plan_pairs((int)half, (int)((160 * 1024) / mf_bfly_row_bytes(n)), ctx->mfma_wgs ? ctx->mfma_wgs : ctx->n_cus, &a)) {
-            const uint32_t* tab;
-            std::array<size_t, 5> aux = {0, 0, 0, 0, 0};
-            rc = get_table(ctx, key("mfinv", {n}, ctx->impl), [&] {
-                const std::vector<HFr> el = domain_elements<HFr>(n, n);  // el[k] = omega^k
-                const HFr ninv = HFr::from_u64(n).inv();
-                std::vector<std::vector<HFr>> C(n, std::vector<HFr>(n));
-                for (size_t i = 0; i < n; ++i)
-                    for (size_t k = 0; k < n; ++k) C[i][k] = el[(n - (i * k) % n) % n] * ninv;  // omega^(-i k) / n
-                std::vector<uint32_t> tbl = build_mfma_bfly_table(C, n, half);
-                aux[0] = tbl.size();
-                return tbl;
-            }, &tab, &aux);
-            if (rc != ShareSuccess) return rc;
-            if (aux[0] != 0) {
-                a.in = (const uint8_t*)evals_dev, a.G = G, a.in_chunk_major = 0, a.row_stride = row_stride ? row_stride : G;
-                for (size_t k = 0; k < n; ++k) a.rows.set(k, (unsigned)ss.rows[k]);  // input k = the share of party k
-                a.table = (const uint8_t*)tab, a.nv = 0, a.half = (int)half, a.nout = (int)n;
-                a.out = (uint8_t*)coeffs_out_dev, a.out_party_major = 0, a.out_stride = n;
-                if (c0_out_dev && degree_out_dev && ctx->list_rows_in_kernel)  // only coefficient 0 is stored (DEG instances: n = 8, 16)
-                    a.out = (uint8_t*)c0_out_dev, a.out_stride = 1, a.store_rows = 1;
-                const int mi = (int)n;
-                a.ncoeffs = degree_out_dev;  // the kernel writes the degrees itself where an instance for it exists (n = 8, 16)
-                done = launch_mfma_bfly(mi, a, ctx->device, s);
-                if (done && degree_out_dev) degree_in_kernel = true;
-                if (!done && degree_out_dev) {
-                    a.ncoeffs = nullptr;
-                    a.out = (uint8_t*)coeffs_out_dev, a.out_stride = n, a.store_rows = 0;
-                    done = launch_mfma_bfly(mi, a, ctx->device, s);
+        const uint32_t* tab;
+        std::array<size_t, 5> aux = {0, 0, 0, 0, 0};
+        rc = get_table(ctx, key("mfinv", {n}, ctx->impl), [&] {
+            const std::vector<HFr> el = domain_elements<HFr>(n, n);  // el[k] = omega^k
+            const HFr ninv = HFr::from_u64(n).inv();
+            std::vector<std::vector<HFr>> C(n, std::vector<HFr>(n));
+            for (size_t i = 0; i < n; ++i)
+                for (size_t k = 0; k < n; ++k) C[i][k] = el[(n - (i * k) % n) % n] * ninv;  // omega^(-i k) / n
+            std::vector<uint32_t> tbl = build_mfma_bfly_table(C, n, half);
+            aux[0] = tbl.size();
+            return tbl;
+        }, &tab, &aux);
+        if (rc != ShareSuccess) return rc;
+        if (aux[0] != 0) {
+            mf::MfmaRowsArgs a;
+            memset(&a, 0, sizeof a);
+            mf::mf_take_plan(plan.pairs, &a);
+            a.in = (const uint8_t*)evals_dev, a.G = G, a.in_chunk_major = 0, a.row_stride = row_stride ? row_stride : G;
+            for (size_t k = 0; k < n; ++k) a.rows.set(k, (unsigned)ss.rows[k]);  // input k = the share of party k
+            a.table = (const uint8_t*)tab, a.nv = 0, a.half = (int)half, a.nout = (int)n;
+            for (int i = 0; i < plan.count && !done; ++i) {
+                a.ncoeffs = nullptr, a.out = (uint8_t*)coeffs_out_dev, a.out_stride = n, a.store_rows = 0;
+                if (plan.route[i] == InterpKernel::IdftDegrees) {
+                    a.ncoeffs = degree_out_dev;  // the kernel writes the degrees itself where an instance for it exists (n = 8, 16)
+                    if (plan.c0_only) a.out = (uint8_t*)c0_out_dev, a.out_stride = 1, a.store_rows = 1;  // only coefficient 0 is stored
+                    done = degree_in_kernel = launch_mfma_bfly((int)n, a, ctx->device, s);
+                } else if (plan.route[i] == InterpKernel::Idft) {
+                    done = launch_mfma_bfly((int)n, a, ctx->device, s);
                 }
-                if (done && degree_in_kernel && a.store_rows == 1) {
-                    HIP_TRY(ctx, hipGetLastError());
-                    return ShareSuccess;  // c0 and the degrees are written
-                }
-                if (done) HIP_TRY(ctx, hipGetLastError());
             }
+            if (done) HIP_TRY(ctx, hipGetLastError());
+            if (degree_in_kernel && plan.c0_only) return ShareSuccess;  // c0 and the degrees are written
         }
     }
-    // otherwise: interpolation through S points == batch_recover with degree S-1 and no redundancy (t = 0): the
-    // verify set is empty and every chunk takes the S x S Lagrange mat-vec
-    if (!done) rc = batch_recover_dev(ctx, ids, S, evals_dev, G, n, S - 1, 0, coeffs_out_dev, nullptr, nullptr, nullptr, false, stream, row_stride);
+    if (!done)
+        rc = batch_recover_dev(ctx, {.sender_ids = ids, .S = S, .evals = evals_dev, .row_stride = row_stride, .G = G, .n = n, .d = S - 1, .t = 0,
+                                     .out = coeffs_out_dev, .stream = stream});
     if (rc != ShareSuccess) return rc;
     if (degree_out_dev && !degree_in_kernel) {  // one pass for the degree and, where asked for, the constant term
         launch_poly_degree((const uint64_t*)coeffs_out_dev, G, (int)S, (int)(ebytes(ctx) / 8), degree_out_dev, pick(ctx, stream), (uint64_t*)c0_out_dev);
@@ -1007,9 +952,10 @@ static ShareErrorCode nonrobust_recover_any(hbmpc_ctx* ctx, const size_t* ids, c
             if (ctx->list_rows_in_kernel) {                                                                               \
                 /* groups that follow each other inside the sender rows (group_stride == G) are one plain call of groups * G chunks */ \
                 const bool dense = group_stride == G;                                                                     \
-                const ShareErrorCode rc = batch_recover_dev(ctx, ids, S, evals_dev, groups * G, n, d, S - d - 1, sel_out_dev, nullptr, \
-                                                            status_out_dev, nullptr, false, stream, row_stride, nullptr, false, \
-                                                            nullptr, 0, (int)d, dense ? 0 : G, dense ? 0 : group_stride);  \
+                const ShareErrorCode rc = batch_recover_dev(                                                              \
+                    ctx, {.sender_ids = ids, .S = S, .evals = evals_dev, .row_stride = row_stride, .G = groups * G, .n = n, .d = d, \
+                          .t = S - d - 1, .out = sel_out_dev, .status = status_out_dev, .stream = stream, .second_coeff = (int)d, \
+                          .group = dense ? 0 : G, .group_stride = dense ? 0 : group_stride});                             \
                 if (rc != HBMPC_NOT_FUSED) return rc;                                                                     \
             }                                                                                                             \
             for (size_t q = 0; q < groups; ++q) {                                                                         \
@@ -1022,9 +968,9 @@ static ShareErrorCode nonrobust_recover_any(hbmpc_ctx* ctx, const size_t* ids, c
         }                                                                                                                 \
         /* the S points on a polynomial of degree <= d?  d + 1 of them interpolate, the others verify; coefficients 0, d */ \
         if (ctx->list_rows_in_kernel) {                                                                                   \
-            const ShareErrorCode rc = batch_recover_dev(ctx, ids, S, evals_dev, G, n, d, S - d - 1, sel_out_dev, nullptr, \
-                                                        status_out_dev, nullptr, false, stream, row_stride, nullptr, false, \
-                                                        nullptr, 0, (int)d);                                              \
+            const ShareErrorCode rc = batch_recover_dev(ctx, {.sender_ids = ids, .S = S, .evals = evals_dev, .row_stride = row_stride, \
+                                                              .G = G, .n = n, .d = d, .t = S - d - 1, .out = sel_out_dev,        \
+                                                              .status = status_out_dev, .stream = stream, .second_coeff = (int)d}); \
             if (rc != HBMPC_NOT_FUSED) return rc;                                                                         \
         }                                                                                                                 \
         /* other shapes: the full interpolation through all S points, then the same two coefficients and the verdict */   \

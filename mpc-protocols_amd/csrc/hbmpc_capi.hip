@@ -27,6 +27,7 @@
 #include "kernels_mfma.hpp"
 #include "kernels_mfma_gl.hpp"
 #include "encode_route.hpp"
+#include "recover_route.hpp"
 #include "kernels_sqrt.hpp"
 #include "tables_sqrt.hpp"
 
@@ -61,8 +62,7 @@ struct hbmpc_ctx {
     bool direct_fail = true;                       // a decode with no OEC round (S == d + t + 1) is ONE launch: failures are written by the first kernel
     bool zero_copy = true;                         // small host-pointer calls stage through mapped host memory
     bool matrix_cores = true;                      // large Fr decodes run the int8 MFMA formulation (kernels_mfma.hpp)
-    size_t mfma_min_chunks = 65536;                // A/B aid since the tables are expanded on the device: the thresholds below decide
-    size_t mfma_min_cached = 4096;                 // ... from this many chunks on (the crossover with the wave-per-chunk kernels)
+    size_t mfma_min_cached = 4096;                 // Fr decodes take the matrix cores from this many chunks on (the crossover with the wave-per-chunk kernels)
     size_t mfma_min_direct = 2048;                 // ... and from this many when the call has no OEC round (one launch)
     size_t mfma_min_encode = 2049;                 // encodes (one table per (n, d), never rebuilt): right above the wave-per-chunk range
     int lazy_fallback_tables = 1;                  // a new sender set's OEC / Gao and second-chance tables are built when a chunk needs them: 1 = host-pointer calls, 2 = all
@@ -252,6 +252,29 @@ static void set_scratch_dirty(hbmpc_ctx* ctx, hipStream_t s, bool dirty) {
     auto it = ctx->scratch.find(s);
     if (it != ctx->scratch.end()) it->second.dirty = dirty;
 }
+// The decodes (batch_recover_dev and the one-launch protocol kernels) share the counters at the start of the stream's scratch
+// (`bytes` of it; [0, 32) u32: counters[0..4), the local summary, the sub-tickets of finish_direct).  They are zero because the last
+// kernel of the previous call on this stream left them so (k_unscale, or the last block of a one-launch kernel).  Fresh scratch,
+// or a call that failed between its first and last launch, is the exception: then they are cleared here.  A graph capture records
+// the clear under the same condition (as a node it costs ~4 us per decode and replay, more than a small decode itself): a replay
+// finds the counters at zero because whatever ran before it on the stream left them so, and hbmpc_graph_launch clears them itself
+// when a call has failed since (the scratch is then marked dirty).
+// Two threads may drive one context (and so one stream): the launches of `enqueue(counters)` reach the stream as one uninterrupted
+// sequence.  When it returns ShareSuccess its last kernel has left the counters at zero, and the scratch is marked clean again.
+template <class Enqueue>
+static ShareErrorCode with_decode_counters(hbmpc_ctx* ctx, hipStream_t s, size_t bytes, Enqueue enqueue) {
+    std::lock_guard<std::mutex> enqueue_lock(ctx->enqueue_mu);
+    void* scratch;
+    bool dirty = false;
+    ShareErrorCode rc = get_scratch(ctx, s, bytes, &scratch, &dirty);
+    if (rc != ShareSuccess) return rc;
+    uint32_t* counters = (uint32_t*)scratch;
+    if (dirty) HIP_TRY(ctx, hipMemsetAsync(counters, 0, 128, s));
+    set_scratch_dirty(ctx, s, true);
+    rc = enqueue(counters);
+    if (rc == ShareSuccess) set_scratch_dirty(ctx, s, false);
+    return rc;
+}
 static std::string key(const char* kind, std::initializer_list<size_t> v, int impl) {
     std::string k = kind;
     for (size_t x : v) k += ":" + std::to_string(x);
@@ -372,7 +395,6 @@ extern "C" ShareErrorCode hbmpc_set_matrix_cores(hbmpc_ctx* ctx, int on, size_t 
         ctx->mfma_min_gold = std::min<size_t>(min_chunks, 4096);
         ctx->mfma_min_gold_direct = std::min<size_t>(min_chunks, 2048);
         ctx->mfma_min_gold_oec = std::min<size_t>(min_chunks, 8193);
-        ctx->mfma_min_chunks = min_chunks;
         ctx->mfma_min_cached = std::min<size_t>(min_chunks, 4096);
         ctx->mfma_min_direct = std::min<size_t>(min_chunks, 2048);
         ctx->mfma_min_encode = std::min<size_t>(min_chunks, 2049);
@@ -2120,13 +2142,7 @@ static ShareErrorCode triplegen_parties_any(hbmpc_ctx* ctx, const T* a, const T*
         const int impl = ctx->impl;
         TripleGenWgArgs ta;
         memset(&ta, 0, sizeof ta);
-        const std::shared_ptr<const DomainInv<H>> dom = domain_inv<H>(ctx, n);
-        ShareErrorCode rc = get_table(ctx, ids_key("rec", ids, n, n, d, t, impl), [&] {
-            RecoverTables T2 = build_recover_tables<H>(*dom, ids, d, t, impl);
-            std::vector<uint32_t> both = T2.vm;
-            both.insert(both.end(), T2.bc.begin(), T2.bc.end());
-            return both;
-        }, &ta.tab);
+        ShareErrorCode rc = rec_table<H>(ctx, *domain_inv<H>(ctx, n), ids, n, d, t, &ta.tab);
         if (rc != ShareSuccess) return rc;
         rc = vmat_table<H>(ctx, n, d, &ta.vmat);
         if (rc != ShareSuccess) return rc;
@@ -2135,20 +2151,14 @@ static ShareErrorCode triplegen_parties_any(hbmpc_ctx* ctx, const T* a, const T*
         ta.a = (const uint32_t*)a, ta.b = (const uint32_t*)b, ta.r2t = (const uint32_t*)r2t, ta.rt = (const uint32_t*)rt;
         ta.Y = (uint32_t*)y_ws, ta.Z = (uint32_t*)z_ws, ta.opened = (uint32_t*)opened_out, ta.c = (uint32_t*)c_out, ta.status = status_out;
         ta.G = G, ta.N = N, ta.n = (int)n, ta.t = (int)t;
-        std::lock_guard<std::mutex> enqueue_lock(ctx->enqueue_mu);
-        void* scratch;
-        bool dirty = false;
-        rc = get_scratch(ctx, s, 2048, &scratch, &dirty);
-        if (rc != ShareSuccess) return rc;
-        ta.counters = (uint32_t*)scratch;
-        ta.summary_first = summary_first_dev ? (uint32_t*)summary_first_dev : ta.counters + 4;
-        ta.summary = summary_dev ? (uint32_t*)summary_dev : ta.counters + 4;
-        if (dirty) HIP_TRY(ctx, hipMemsetAsync(ta.counters, 0, 128, s));
-        set_scratch_dirty(ctx, s, true);
-        launch_triplegen_wg(impl, ta, s);
-        HIP_TRY(ctx, hipGetLastError());
-        set_scratch_dirty(ctx, s, false);  // the kernel's last workgroup leaves the counters at zero
-        return ShareSuccess;
+        return with_decode_counters(ctx, s, 2048, [&](uint32_t* counters) -> ShareErrorCode {
+            ta.counters = counters;
+            ta.summary_first = summary_first_dev ? (uint32_t*)summary_first_dev : counters + 4;
+            ta.summary = summary_dev ? (uint32_t*)summary_dev : counters + 4;
+            launch_triplegen_wg(impl, ta, s);
+            HIP_TRY(ctx, hipGetLastError());
+            return ShareSuccess;  // the kernel's last workgroup leaves the counters at zero
+        });
     }
     // [ab - r]_2t Vandermonde-encoded in chunks of 2t + 1 for every recipient (batch_recon.rs:157-165), all parties in one launch;
     // EvalBatch arm for ALL recipients in one call: the row of sender p for "chunk" j G + g is y_ws + p (n G) + (j G + g);
@@ -2246,21 +2256,14 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
             fa.de_out = (uint32_t*)de_out, fa.z = (uint32_t*)z_out, fa.r_dash = (uint32_t*)r_dash_out, fa.open_sh = (uint32_t*)open_sh_out;
             fa.out = (uint32_t*)d_out, fa.c_open = (uint32_t*)c_open_out, fa.status = status_out;
             for (size_t i = 0; i < S; ++i) fa.rows.set(i, (unsigned)ss.ids[i]);  // the per-party arrays are indexed by party id
-            // the decodes' counters (see batch_recover_dev): zero between calls, cleared here only when that is not known
-            std::lock_guard<std::mutex> enqueue_lock(ctx->enqueue_mu);
-            void* scratch;
-            bool dirty = false;
-            rc = get_scratch(ctx, s, 2048, &scratch, &dirty);
-            if (rc != ShareSuccess) return rc;
-            fa.counters = (uint32_t*)scratch;
-            fa.summary_first = summary_first_dev ? (uint32_t*)summary_first_dev : fa.counters + 4;  // the scratch's local summary slot
-            fa.summary = summary_dev ? (uint32_t*)summary_dev : fa.counters + 4;
-            if (dirty) HIP_TRY(ctx, hipMemsetAsync(fa.counters, 0, 128, s));
-            set_scratch_dirty(ctx, s, true);
-            launch_fpmul_wave(fa, ctx->device, s, false);
-            HIP_TRY(ctx, hipGetLastError());
-            set_scratch_dirty(ctx, s, false);  // the kernel's last workgroup leaves the counters at zero
-            return ShareSuccess;
+            return with_decode_counters(ctx, s, 2048, [&](uint32_t* counters) -> ShareErrorCode {
+                fa.counters = counters;
+                fa.summary_first = summary_first_dev ? (uint32_t*)summary_first_dev : counters + 4;  // the scratch's local summary slot
+                fa.summary = summary_dev ? (uint32_t*)summary_dev : counters + 4;
+                launch_fpmul_wave(fa, ctx->device, s, false);
+                HIP_TRY(ctx, hipGetLastError());
+                return ShareSuccess;  // the kernel's last workgroup leaves the counters at zero
+            });
         }
     }
     // the shares Multiply opens (multiplication.rs:417-426) and reconstruct_rbc's recover_secret of a - x and of b - y (:102-139):
@@ -2271,7 +2274,8 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
     ShareErrorCode rc = HBMPC_NOT_FUSED;
     if (N >= ctx->pair_decode_min) {
         PairInput pi = {(const uint32_t*)a, (const uint32_t*)b, (const uint32_t*)x, (const uint32_t*)y, N};
-        rc = batch_recover_dev(ctx, sender_ids, S, nullptr, 2 * N, n, t, t, de_out, nullptr, status_out, summary_first_dev, true, stream, 0, nullptr, false, &pi);
+        rc = batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .G = 2 * N, .n = n, .d = t, .t = t, .out = de_out, .status = status_out,
+                                     .summary = summary_first_dev, .p0 = true, .stream = stream, .pair = &pi});
     }
     if (rc == HBMPC_NOT_FUSED) {
         rc = hbmpc_dev_beaver_open_shares_paired(ctx, a, b, x, y, N, n, de_sh_ws, stream);

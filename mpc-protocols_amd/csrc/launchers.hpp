@@ -86,8 +86,7 @@ void launch_recover_generic(int impl, bool p0, const RecoverArgs& ra, unsigned g
 // team: the workgroup-per-tile form for batches with fewer tiles than waves (kernels_mfma_team.hpp)
 namespace mf { struct MfmaRowsArgs; struct MfmaGlArgs; }
 bool launch_mfma_rows_gl(const mf::MfmaGlArgs& a, unsigned grid, int device, hipStream_t s);  // Goldilocks (kernels_mfma_gl.hpp)
-// the decode whose sender values are differences formed after loading (k_mfma_rows<.., SUB>), m = 2 .. 11
-bool mfma_sub_covers(int m);
+// the decode whose sender values are differences formed after loading (k_mfma_rows<.., SUB>), m = 2 .. MF_SUB_MAX_M (tables_mfma.hpp)
 bool launch_mfma_rows_sub(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s);
 bool launch_mfma_rows_a(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s, bool team = false);
 bool launch_mfma_rows_b(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s, bool team = false);

@@ -39,6 +39,9 @@ inline int mf_row_of_digit(int b) {
 // per-digit bias magnitude: |sum s d| <= 32 m * 128 * 128
 inline uint32_t mf_bias_mag(size_t m) { return (uint32_t)(32 * m * 16384); }
 constexpr size_t MF_MAX_M = 15;  // digit sums < 2 * 32 m * 16384 + 512 must stay below 0xff0000
+// the decode whose sender values are differences formed after loading (k_mfma_rows<.., SUB>, tu_mfma_sub.hip): m = 2 .. 11
+constexpr size_t MF_SUB_MAX_M = 11;
+inline bool mfma_sub_covers(size_t m) { return m >= 2 && m <= MF_SUB_MAX_M; }
 
 namespace mfdetail {
 // plain 256-bit integers mod r (canonical, little-endian u64 words): the table needs 32 m shifted copies of every

@@ -3,6 +3,7 @@
 
 #include "kernels_mfma.hpp"
 #include "launchers.hpp"
+#include "tables_mfma.hpp"
 namespace hbmpc {
 namespace {
 // the raw operands of the next tile (2 m registers of 4) wait beside the current tile's m: fewer waves than the plain kernel
@@ -24,8 +25,7 @@ bool range(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s, std::int
     return hit;
 }
 }  // namespace
-bool mfma_sub_covers(int m) { return m >= 2 && m <= 11; }
 bool launch_mfma_rows_sub(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s) {
-    return range<2>(m, a, device, s, std::make_integer_sequence<int, 10>{});
+    return range<2>(m, a, device, s, std::make_integer_sequence<int, (int)MF_SUB_MAX_M - 1>{});
 }
 }  // namespace hbmpc
