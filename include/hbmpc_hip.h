@@ -52,7 +52,8 @@ typedef struct {
 
 /* ffi/c_bindings/share/mod.rs:18-37 (same order, same values).  The HBMPC_* values are this library's: 100 and 101 report
  * conditions the Rust code cannot have; 102 and 103 carry the two RandBitError variants of phase 2
- * (fpmul/rand_bit.rs:197-220), which the reference reports through its own error type, not through ShareErrorCode. */
+ * (fpmul/rand_bit.rs:197-220) and 104 PRandError::SurpassedFieldCapacity (fpmul/prandbitd.rs:506-517), which the reference reports
+ * through its own error types, not through ShareErrorCode. */
 typedef enum {
     ShareSuccess = 0,
     InsufficientShares = 1,
@@ -66,7 +67,8 @@ typedef enum {
     HBMPC_NO_DEVICE = 100,    /* no HIP device / HIP runtime error (see hbmpc_last_error) */
     HBMPC_OUT_OF_MEMORY = 101, /* device allocation failed */
     HBMPC_ZERO_SQUARE = 102,   /* RandBitError::ZeroSquare: an opened square a^2 is zero (rand_bit.rs:198-202) */
-    HBMPC_NO_SQUARE_ROOT = 103 /* RandBitError::SquareRoot: an opened square has no root (rand_bit.rs:206) */
+    HBMPC_NO_SQUARE_ROOT = 103, /* RandBitError::SquareRoot: an opened square has no root (rand_bit.rs:206) */
+    HBMPC_FIELD_CAPACITY = 104  /* PRandError::SurpassedFieldCapacity: k + l + 2 + ceil(log2 n) >= 64 (prandbitd.rs:506-517) */
 } ShareErrorCode;
 
 /* ffi/c_bindings/share/mod.rs:50-53 (FieldKind).  Goldilocks64 is this library's extension for the reference's small
@@ -833,6 +835,48 @@ ShareErrorCode hbmpc_dev_randbit_finalize_parties(hbmpc_ctx* ctx, const U256* a,
                                                   uint8_t* status_out, hbmpc_randbit_summary* summary_dev, void* stream);
 ShareErrorCode hbmpc_gl_dev_randbit_finalize_parties(hbmpc_ctx* ctx, const uint64_t* a, const uint64_t* opened_sq, size_t N, size_t parties,
                                                      uint64_t* out, uint8_t* status_out, hbmpc_randbit_summary* summary_dev, void* stream);
+
+/* ==== PRandBit / PRandInt: RISS-to-Shamir conversion (csrc/kernels_riss.hpp; fpmul/prandbitd.rs) ================================
+ * PRandBitDNode<Goldilocks, Fr> lifts a Goldilocks bit to an Fr bit and a GF(2^8) bit (PRandBit) and makes Fr random integers
+ * (PRandInt).  Every party sends a value r_T <= 2^(l+k) per maximal unqualified set T (the t-subsets of 0..n) to the parties outside
+ * T; the sums over the n senders are the replicated shares, converted locally to Shamir shares in each field.  A folded r_T is a
+ * plain integer below 2^62, one uint64_t, in either field.  Supported shapes: n >= 3t + 1 and C(n, t) <= 8192 (and C(n, t) n <= 2^20
+ * table entries); others return InvalidInput.  Not here: sampling the r_T, sessions, messages.
+ * Coefficient tables are built per context and (n, t) at the first call (run it once before a graph capture). */
+/* the sets in the order every call below indexes them: combinations(0..n, t), lexicographic (prandbitd.rs:479).  *count_out = C(n, t)
+ * (InvalidInput beyond 8192); ids_out (nullable) receives count x t ids.  Host only: needs no context and no device. */
+ShareErrorCode hbmpc_riss_tsets(size_t n, size_t t, size_t* ids_out, size_t* count_out);
+/* replaces the fold of prandbitd.rs:667-684 with the bound test of :638-647, for either kind of context: contrib [n][Tn][B] the
+ * senders' values -> sums_out [Tn][B], bad_out [n][Tn] bytes: 1 where any value of (sender, set) exceeds 2^lk_bits (the reference's
+ * InvalidMessage; the bound itself is allowed).  The sums always include all n contributions -- the reference rejects the offending
+ * message instead -- so the caller reads the verdicts and drops or re-requests those sets; sums of sets without a verdict are exact.
+ * lk_bits + 2 + ceil(log2 n) >= 64 returns HBMPC_FIELD_CAPACITY (prandbitd.rs:506-517). */
+ShareErrorCode hbmpc_dev_riss_fold(hbmpc_ctx* ctx, const uint64_t* contrib, size_t n, size_t Tn, size_t B, size_t lk_bits, uint64_t* sums_out,
+                                   uint8_t* bad_out, void* stream);
+/* replaces the conversion of try_advance_from_riss (prandbitd.rs:311-356): out[p][i] = sum_T r[T][i] f_T(alpha_j), j = party_ids[p],
+ * in the context's field, and (out2 non-NULL; n <= 255, Gf256Domain::new) out2[p][i] = xor_T (r[T][i] & 1) f2_T(3^j) in GF(2^8) with
+ * the AES polynomial.  own_sets_only = 0: r [C(n,t)][B] over every set, read once for all the parties of the call (a set that
+ * contains j has coefficient zero for j); party_ids NULL means parties = n, party p = p.  own_sets_only = 1: what a deployed node
+ * calls -- parties = 1, party_ids[0] = j, r [C(n-1,t)][B] over j's own sets, in combinations order with the sets that contain j
+ * skipped (prandbitd.rs:483-487).  Every r value must be below 2^62 (the capacity check of the fold guarantees it). */
+ShareErrorCode hbmpc_dev_riss_convert_parties(hbmpc_ctx* ctx, const uint64_t* r, size_t n, size_t t, size_t B, const size_t* party_ids,
+                                              size_t parties, int own_sets_only, U256* out, uint8_t* out2_or_null, void* stream);
+ShareErrorCode hbmpc_gl_dev_riss_convert_parties(hbmpc_ctx* ctx, const uint64_t* r, size_t n, size_t t, size_t B, const size_t* party_ids,
+                                                 size_t parties, int own_sets_only, uint64_t* out, uint8_t* out2_or_null, void* stream);
+ShareErrorCode hbmpc_riss_convert_parties(hbmpc_ctx* ctx, const uint64_t* r, size_t n, size_t t, size_t B, const size_t* party_ids,
+                                          size_t parties, int own_sets_only, U256* out, uint8_t* out2_or_null);
+ShareErrorCode hbmpc_gl_riss_convert_parties(hbmpc_ctx* ctx, const uint64_t* r, size_t n, size_t t, size_t B, const size_t* party_ids,
+                                             size_t parties, int own_sets_only, uint64_t* out, uint8_t* out2_or_null);
+/* replaces the arithmetic of try_finalize_bit (prandbitd.rs:189-211) for `parties` parties (an Fr context): opened [B] the opened
+ * r + b (canonical Goldilocks values), r_p [parties][B], r_2 [parties][B] bytes -> bp_out[p][i] = G(opened[i]) - r_p[p][i],
+ * b2_out[p][i] = r_2[p][i] ^ lsb(opened[i]). */
+ShareErrorCode hbmpc_dev_prandbit_finalize_parties(hbmpc_ctx* ctx, const uint64_t* opened, const U256* r_p, const uint8_t* r_2, size_t B,
+                                                   size_t parties, U256* bp_out, uint8_t* b2_out, void* stream);
+ShareErrorCode hbmpc_prandbit_finalize_parties(hbmpc_ctx* ctx, const uint64_t* opened, const U256* r_p, const uint8_t* r_2, size_t B,
+                                               size_t parties, U256* bp_out, uint8_t* b2_out);
+/* A/B aid: how the conversion lays its work out.  0 = by size (default), 1 = always a workgroup per 64 elements and 16 parties,
+ * 2 = always a workgroup per 64 elements and party with the sets in four slices.  Same results. */
+ShareErrorCode hbmpc_set_riss_form(hbmpc_ctx* ctx, int form);
 
 /* ---- A/B aid: 0 = unsaturated 9x29-bit limbs (default, fast), 1 = saturated 8x32-bit limbs
  * (the straightforward formulation; same results, kept as a cross-check). */

@@ -19,6 +19,7 @@
 #pragma once
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "hbmpc_hip.h"
 
@@ -212,6 +213,90 @@ class Preprocessing : public Pipeline {
         pl_check(hbmpc_pipe_part(h_, name, &p), ctx_, name);
         return p;
     }
+};
+
+// PRandInt and PRandBit (fpmul/prandbitd.rs) for all n parties.  They span two fields -- a Goldilocks context and an Fr context on
+// the same device -- so they are compositions of device calls on one stream, not hbmpc_pipe handles (no graph replay here).
+// Buffers are device memory owned by the object; inputs: contrib [n][C(n,t)][B] uint64_t the senders' RISS values (and, PRandBit,
+// b_q [n][B] the Goldilocks shares of the bits).
+class PRandInt {
+  public:
+    // fold -> sums [C(n,t)][B], bad [n][C(n,t)] verdict bytes; convert over Fr -> r_p [n][B] (prandbitd.rs:667-684, 311-356).  Any B.
+    PRandInt(hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t B, void* stream) : n(n), t(t), B(B), fr_(ctx_fr), stream_(stream) {
+        pl_check(stream ? ShareSuccess : InvalidInput, fr_, "PRandInt needs an explicit stream");
+        pl_check(hbmpc_riss_tsets(n, t, nullptr, &tsets), fr_, "hbmpc_riss_tsets");
+        contrib = alloc<uint64_t>(n * tsets * B), sums = alloc<uint64_t>(tsets * B), bad = alloc<uint8_t>(n * tsets), r_p = alloc<U256>(n * B);
+    }
+    virtual ~PRandInt() {
+        for (void* p : owned_) hbmpc_dev_free(fr_, p);
+    }
+    PRandInt(const PRandInt&) = delete;
+    PRandInt& operator=(const PRandInt&) = delete;
+    void run(size_t lk_bits) { fold_and_fr(lk_bits, nullptr); }
+    void sync() { pl_check(hbmpc_stream_sync(fr_, stream_), fr_, "sync"); }
+    const size_t n, t, B;
+    size_t tsets = 0;
+    uint64_t *contrib, *sums;
+    uint8_t* bad;
+    U256* r_p;
+
+  protected:
+    template <class T>
+    T* alloc(size_t count) {
+        void* p = nullptr;
+        pl_check(hbmpc_dev_alloc(fr_, (count ? count : 1) * sizeof(T), &p), fr_, "hbmpc_dev_alloc");
+        owned_.push_back(p);
+        return static_cast<T*>(p);
+    }
+    void fold_and_fr(size_t lk_bits, uint8_t* r_2) {
+        pl_check(hbmpc_dev_riss_fold(fr_, contrib, n, tsets, B, lk_bits, sums, bad, stream_), fr_, "hbmpc_dev_riss_fold");
+        pl_check(hbmpc_dev_riss_convert_parties(fr_, sums, n, t, B, nullptr, n, 0, r_p, r_2, stream_), fr_, "hbmpc_dev_riss_convert_parties");
+    }
+    hbmpc_ctx* fr_;
+    void* stream_;
+    std::vector<void*> owned_;
+};
+
+// fold; convert over Fr -> r_p, r_2 (GF(2^8)) and over Goldilocks -> r_q; rb = r_q + b_q; BatchRecon of rb in chunks of t + 1 from all
+// n senders (prandbitd.rs:437-446: the encode, the recipients' P(0) decodes, the coefficient decode; up to t wrong senders are
+// corrected) -> opened [B]; finalize -> b_p [n][B] Fr, b_2 [n][B] bytes (prandbitd.rs:189-211).  B a multiple of t + 1
+// (PRandError::Incompatible; here InvalidInput).
+class PRandBit : public PRandInt {
+  public:
+    PRandBit(hbmpc_ctx* ctx_gl, hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t B, void* stream) : PRandInt(ctx_fr, n, t, B, stream), gl_(ctx_gl) {
+        pl_check(B % (t + 1) == 0 ? ShareSuccess : InvalidInput, fr_, "B must be a multiple of t + 1");
+        G = B / (t + 1);
+        b_q = alloc<uint64_t>(n * B), r_q = alloc<uint64_t>(n * B), rb = alloc<uint64_t>(n * B), Y = alloc<uint64_t>(n * n * G);
+        Z = alloc<uint64_t>(n * G), opened = alloc<uint64_t>(B), r_2 = alloc<uint8_t>(n * B), b_2 = alloc<uint8_t>(n * B), b_p = alloc<U256>(n * B);
+        rstatus = alloc<uint8_t>(n * G), summary_first = alloc<hbmpc_recover_summary>(1), summary = alloc<hbmpc_recover_summary>(1);
+        for (size_t i = 0; i < n; ++i) ids_.push_back(i);
+    }
+    void prepare(size_t lk_bits) {  // everything before the messages of the open are exchanged
+        fold_and_fr(lk_bits, r_2);
+        pl_check(hbmpc_gl_dev_riss_convert_parties(gl_, sums, n, t, B, nullptr, n, 0, r_q, nullptr, stream_), gl_, "hbmpc_gl_dev_riss_convert_parties");
+        pl_check(hbmpc_gl_dev_fr_op(gl_, 0, r_q, b_q, n * B, rb, stream_), gl_, "r + b");
+        pl_check(hbmpc_gl_dev_vandermonde_apply_parties(gl_, rb, G, n, t, n, Y, stream_), gl_, "open: encode");
+    }
+    void finish() {
+        pl_check(hbmpc_gl_dev_batch_recover_strided(gl_, ids_.data(), n, Y, n * G, n * G, n, t, t, 1, Z, nullptr, rstatus, summary_first, stream_), gl_,
+                 "open: P(0) decodes");
+        pl_check(hbmpc_gl_dev_batch_recover(gl_, ids_.data(), n, Z, G, n, t, t, opened, nullptr, rstatus, summary, stream_), gl_,
+                 "open: coefficient decode");
+        pl_check(hbmpc_dev_prandbit_finalize_parties(fr_, opened, r_p, r_2, B, n, b_p, b_2, stream_), fr_, "hbmpc_dev_prandbit_finalize_parties");
+    }
+    void run(size_t lk_bits) {
+        prepare(lk_bits);
+        finish();
+    }
+    size_t G = 0;  // chunks of the open
+    uint64_t *b_q, *r_q, *rb, *Y, *Z, *opened;
+    uint8_t *r_2, *b_2, *rstatus;
+    U256* b_p;
+    hbmpc_recover_summary *summary_first, *summary;  // device memory: the two decodes of the open
+
+  private:
+    hbmpc_ctx* gl_;
+    std::vector<size_t> ids_;
 };
 
 }  // namespace hbmpc

@@ -30,6 +30,8 @@
 #include "recover_route.hpp"
 #include "kernels_sqrt.hpp"
 #include "tables_sqrt.hpp"
+#include "kernels_riss.hpp"
+#include "tables_riss.hpp"
 
 using namespace hbmpc;
 
@@ -81,6 +83,7 @@ struct hbmpc_ctx {
     std::map<size_t, std::shared_ptr<DomainInv<HFr>>> dom_fr;  // per n: domain elements + inverse differences (tables.hpp), built once
     std::map<size_t, std::shared_ptr<DomainInv<HGl>>> dom_gl;
     int n_cus = 256;
+    int riss_form = 0;                             // RISS conversion (kernels_riss.hpp): 0 = by size, 1 = always 16 parties per workgroup, 2 = always one (A/B aid)
     int mfma_wgs = 0;                              // test aid: workgroups of a matrix-core launch (0 = one per CU)
     std::map<hipStream_t, Scratch> scratch;        // per-stream scratch (calls on one stream are ordered)
     std::vector<std::pair<void*, size_t>> stage_free;  // device staging buffers of the host-pointer API, kept between calls
@@ -2117,6 +2120,7 @@ extern "C" ShareErrorCode hbmpc_dev_check_double_share_c0(hbmpc_ctx* ctx, const 
 }
 
 #include "capi_recover.inc"
+#include "capi_riss.inc"
 
 // ---- TripleGenNode for all parties on this device (triple_gen/triple_generation.rs:304-364) --------------------------------------
 // T: U256 (H = HFr) or uint64_t (H = HGl)

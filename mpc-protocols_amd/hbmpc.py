@@ -63,6 +63,17 @@ def _sz(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.uint64))
 
 
+def riss_tsets(n, t):
+    """(rc, sets): hbmpc_riss_tsets -- combinations(0..n, t) as the library enumerates them; host only, needs no device"""
+    cnt = C.c_size_t()
+    rc = lib().hbmpc_riss_tsets(C.c_size_t(n), C.c_size_t(t), None, C.byref(cnt))
+    if rc != 0:
+        return rc, []
+    ids = np.zeros((cnt.value, t), dtype=np.uint64)
+    rc = lib().hbmpc_riss_tsets(C.c_size_t(n), C.c_size_t(t), _p(ids), C.byref(cnt))
+    return rc, [tuple(int(x) for x in row) for row in ids]
+
+
 class Engine:
     """One hbmpc_ctx on one GPU.  Host-pointer calls take/return numpy U256 arrays; the
     dev_* calls take raw device pointers (ints, e.g. torch.Tensor.data_ptr()) and a stream."""
@@ -550,6 +561,56 @@ class Engine:
         (status << 32) | index, u32 n_failed); returns the ShareErrorCode"""
         return self._f("dev_randbit_finalize_parties")(self.ctx, C.c_void_p(a_d), C.c_void_p(sq_d), C.c_size_t(N), C.c_size_t(parties),
                                                          C.c_void_p(out_d), C.c_void_p(status_d), C.c_void_p(summary_d), C.c_void_p(stream))
+
+    # ---- PRandBit / PRandInt: RISS fold, RISS-to-Shamir conversion, finalize (csrc/kernels_riss.hpp) ----
+    FIELD_CAPACITY = 104  # HBMPC_FIELD_CAPACITY
+
+    def riss_tsets(self, n, t):
+        """(rc, sets) the maximal unqualified sets in the order the conversion indexes r: combinations(0..n, t) (host only)"""
+        return riss_tsets(n, t)
+
+    def dev_riss_fold(self, contrib_d, n, Tn, B, lk_bits, sums_d, bad_d, stream=0):
+        """contrib [n][Tn][B] u64 -> sums [Tn][B] u64, bad [n][Tn] bytes (1: a value of (sender, set) exceeds 2^lk_bits)"""
+        return self.L.hbmpc_dev_riss_fold(self.ctx, C.c_void_p(contrib_d), C.c_size_t(n), C.c_size_t(Tn), C.c_size_t(B), C.c_size_t(lk_bits),
+                                          C.c_void_p(sums_d), C.c_void_p(bad_d), C.c_void_p(stream))
+
+    def dev_riss_convert_parties(self, r_d, n, t, B, out_d, out2_d=0, party_ids=None, own_sets_only=False, stream=0):
+        """r [sets][B] u64 -> out [parties][B] elements of this engine's field, out2 [parties][B] GF(2^8) bytes (0: skipped).
+        party_ids None: all n parties over all C(n,t) sets; own_sets_only: one party over its own C(n-1,t) sets"""
+        ids = None if party_ids is None else _sz(party_ids)
+        parties = n if party_ids is None else len(party_ids)
+        return self._f("dev_riss_convert_parties")(self.ctx, C.c_void_p(r_d), C.c_size_t(n), C.c_size_t(t), C.c_size_t(B), _p(ids),
+                                                     C.c_size_t(parties), C.c_int(1 if own_sets_only else 0), C.c_void_p(out_d),
+                                                     C.c_void_p(out2_d), C.c_void_p(stream))
+
+    def riss_convert_parties(self, r, n, t, party_ids=None, own_sets_only=False, with_gf2=True):
+        """host-pointer form: r [sets][B] u64 -> (rc, out [parties][B], out2 [parties][B] bytes or None)"""
+        r = np.ascontiguousarray(r, dtype=np.uint64)
+        B = r.shape[1]
+        ids = None if party_ids is None else _sz(party_ids)
+        parties = n if party_ids is None else len(party_ids)
+        out = self._new((parties, B))
+        out2 = np.zeros((parties, B), dtype=np.uint8) if with_gf2 else None
+        rc = self._f("riss_convert_parties")(self.ctx, _p(r), C.c_size_t(n), C.c_size_t(t), C.c_size_t(B), _p(ids), C.c_size_t(parties),
+                                               C.c_int(1 if own_sets_only else 0), _p(out), _p(out2))
+        return rc, out, out2
+
+    def dev_prandbit_finalize_parties(self, opened_d, rp_d, r2_d, B, parties, bp_d, b2_d, stream=0):
+        """opened [B] u64 (Goldilocks values), r_p [parties][B] Fr, r_2 [parties][B] bytes -> bp = G(opened) - r_p, b2 = r_2 ^ lsb(opened)"""
+        return self.L.hbmpc_dev_prandbit_finalize_parties(self.ctx, C.c_void_p(opened_d), C.c_void_p(rp_d), C.c_void_p(r2_d), C.c_size_t(B),
+                                                          C.c_size_t(parties), C.c_void_p(bp_d), C.c_void_p(b2_d), C.c_void_p(stream))
+
+    def prandbit_finalize_parties(self, opened, r_p, r_2):
+        """host-pointer form -> (rc, bp [parties][B], b2 [parties][B] bytes)"""
+        opened, r_p, r_2 = np.ascontiguousarray(opened, dtype=np.uint64), np.ascontiguousarray(r_p), np.ascontiguousarray(r_2, dtype=np.uint8)
+        parties, B = r_2.shape
+        bp, b2 = u256((parties, B)), np.zeros((parties, B), dtype=np.uint8)
+        rc = self.L.hbmpc_prandbit_finalize_parties(self.ctx, _p(opened), _p(r_p), _p(r_2), C.c_size_t(B), C.c_size_t(parties), _p(bp), _p(b2))
+        return rc, bp, b2
+
+    def set_riss_form(self, form: int):
+        """A/B aid: 0 by size, 1 a workgroup per 16 parties, 2 a workgroup per party with the sets in slices"""
+        assert self.L.hbmpc_set_riss_form(self.ctx, C.c_int(form)) == 0
 
     # ---- wire codec ----
     def dev_pack_fvec(self, rows_d, row_stride, G, n_rows, payloads_d, payload_stride_bytes, stream=0):

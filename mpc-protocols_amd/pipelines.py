@@ -13,6 +13,9 @@ in the library; this file only names things for the tests and bench.py.
                  double_share/double_share_generation.rs:151-215, ran_dou_sha/mod.rs:371-449,569-602,314-331
   Preprocessing  run_preprocessing's triple part (honeybadger/mod.rs:1239-1393): RanSha -> a, b; RanDouSha -> r; TripleGen
   RandBit        RandBit: Beaver square of a, BatchRecon of a^2, phase 2   fpmul/rand_bit.rs:242-293,197-220
+  PRandInt       fold of the RISS contributions, conversion to Fr shares   fpmul/prandbitd.rs:667-684,311-356
+  PRandBit       ... and to Goldilocks and GF(2^8), open r + b, finalize   fpmul/prandbitd.rs:311-356,437-446,189-211
+PRandInt and PRandBit span two fields, so they are compositions of device calls here, not hbmpc_pipe handles.
 """
 from __future__ import annotations
 
@@ -268,3 +271,135 @@ class RandBit(_Pipe):
         """(first, n_failed) of the finalize"""
         b = self.bytes_of("summary", 16)
         return int(b[:8].view(np.uint64)[0]), int(b[8:12].view(np.uint32)[0])
+
+
+class _Riss:
+    """device buffers of the two RISS compositions: named, allocated once, freed by close()"""
+
+    def __init__(self, eng_fr, n, t, B, stream):
+        if eng_fr.field != "fr":
+            raise RuntimeError("PRandInt / PRandBit -> ShareErrorCode 5: the large field is bls12-381 Fr")
+        self.fr, self.n, self.t, self.B = eng_fr, n, t, B
+        self._own_stream = not stream  # two contexts share the stream, so stream 0 (each context's own) will not do
+        self.stream = stream or eng_fr.stream_create()
+        rc, sets = eng_fr.riss_tsets(n, t)
+        if rc == 0 and (n < 3 * t + 1 or B == 0):
+            rc = 4
+        self._rc(rc, f"shape n = {n}, t = {t}, B = {B}")
+        self.Tn = len(sets)
+        self._bufs = {}
+
+    def _rc(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} -> ShareErrorCode {rc}: {self.fr.last_error()}")
+
+    def _alloc(self, name, nbytes):
+        self._bufs[name] = (self.fr.dev_alloc(max(1, nbytes)), nbytes)
+        return self._bufs[name][0]
+
+    def __getattr__(self, name):  # pipe.contrib, pipe.r_p, ...: the device pointer of that buffer
+        bufs = self.__dict__.get("_bufs", {})
+        if name in bufs:
+            return bufs[name][0]
+        raise AttributeError(name)
+
+    def upload_named(self, name, arr):
+        arr = np.ascontiguousarray(arr)
+        assert arr.nbytes == self._bufs[name][1], (name, arr.nbytes, self._bufs[name][1])
+        self.fr.h2d(self._bufs[name][0], arr, self.stream)
+        self.fr.sync(self.stream)
+
+    def download_named(self, name, dtype, shape):
+        out = np.zeros(shape, dtype=dtype)
+        assert out.nbytes == self._bufs[name][1], (name, out.nbytes, self._bufs[name][1])
+        self.fr.sync(self.stream)
+        self.fr.d2h(out, self._bufs[name][0], self.stream)
+        self.fr.sync(self.stream)
+        return out
+
+    def sync(self):
+        self.fr.sync(self.stream)
+
+    def close(self):
+        for p, _ in self._bufs.values():
+            self.fr.dev_free(p)
+        self._bufs = {}
+        if self._own_stream and self.stream:
+            self.fr.stream_destroy(self.stream)
+            self.stream = 0
+
+    def _fold_and_fr(self, lk_bits, with_gf2):
+        n, t, B = self.n, self.t, self.B
+        self._rc(self.fr.dev_riss_fold(self.contrib, n, self.Tn, B, lk_bits, self.sums, self.bad, self.stream), "hbmpc_dev_riss_fold")
+        self._rc(self.fr.dev_riss_convert_parties(self.sums, n, t, B, self.r_p, self.r_2 if with_gf2 else 0, stream=self.stream),
+                 "hbmpc_dev_riss_convert_parties")
+
+
+class PRandInt(_Riss):
+    """PRandInt for all n parties (prandbitd.rs:667-684, 311-356): contrib [n][C(n,t)][B] u64 the senders' values ->
+    sums [C(n,t)][B], bad [n][C(n,t)] verdict bytes, r_p [n][B] the Fr shares of the random integers.  Any B."""
+
+    def __init__(self, eng_fr, n, t, B, stream=0):
+        super().__init__(eng_fr, n, t, B, stream)
+        self._alloc("contrib", n * self.Tn * B * 8), self._alloc("sums", self.Tn * B * 8), self._alloc("bad", n * self.Tn)
+        self._alloc("r_p", n * B * 32)
+
+    def run(self, lk_bits):
+        self._fold_and_fr(lk_bits, False)
+
+
+class PRandBit(_Riss):
+    """PRandBit for all n parties on one stream (prandbitd.rs:667-684, 311-356, 437-446, 189-211), from a Goldilocks engine and an Fr
+    engine on the same device.  Inputs: contrib [n][C(n,t)][B] u64, b_q [n][B] the Goldilocks shares of the bits.  run():
+      fold -> sums, bad;  convert over Fr -> r_p, r_2 (GF(2^8));  convert over Goldilocks -> r_q;  rb = r_q + b_q (fr_op);
+      BatchRecon of rb in chunks of t + 1 from all n senders (encode, the recipients' P(0) decodes, the coefficient decode;
+      up to t wrong senders are corrected by the decodes' OEC path) -> opened [B];
+      finalize -> b_p [n][B] Fr, b_2 [n][B] bytes.
+    B must be a multiple of t + 1 (PRandError::Incompatible; here ShareErrorCode 4)."""
+
+    def __init__(self, eng_gl, eng_fr, n, t, B, stream=0):
+        super().__init__(eng_fr, n, t, B, stream)
+        if eng_gl.field != "goldilocks":
+            raise RuntimeError("PRandBit -> ShareErrorCode 5: the small field is Goldilocks")
+        if B % (t + 1) != 0:
+            raise RuntimeError(f"PRandBit -> ShareErrorCode 4: B = {B} is not a multiple of t + 1")  # prandbitd.rs:472-476
+        self.gl = eng_gl
+        self.G = G = B // (t + 1)
+        self._alloc("contrib", n * self.Tn * B * 8), self._alloc("sums", self.Tn * B * 8), self._alloc("bad", n * self.Tn)
+        for name in ("r_p", "b_p"):
+            self._alloc(name, n * B * 32)
+        for name in ("r_2", "b_2"):
+            self._alloc(name, n * B)
+        for name in ("b_q", "r_q", "rb"):
+            self._alloc(name, n * B * 8)
+        self._alloc("Y", n * n * G * 8), self._alloc("Z", n * G * 8), self._alloc("opened", B * 8)
+        self._alloc("rstatus", n * G), self._alloc("summary_first", 16), self._alloc("summary", 16)
+        self.ids = list(range(n))
+
+    def open(self):
+        """BatchRecon of rb [party][G (t + 1)] (batch_recon.rs:157-165, 384-391, 457-467): Y [party][recipient][chunk], Z [recipient][chunk]"""
+        n, t, G, gl, st = self.n, self.t, self.G, self.gl, self.stream
+        self._rc(gl.dev_batch_recover_strided(self.ids, self.Y, n * G, n * G, n, t, t, self.Z, p0=True, status_d=self.rstatus,
+                                              summary_d=self.summary_first, stream=st), "open: P(0) decodes")
+        self._rc(gl.dev_batch_recover(self.ids, self.Z, G, n, t, t, self.opened, 0, self.rstatus, self.summary, st), "open: coefficient decode")
+
+    def prepare(self, lk_bits):
+        """everything before the parties' messages of the open are exchanged: ... -> Y, every sender's encoded r + b"""
+        n, t, B, gl, st = self.n, self.t, self.B, self.gl, self.stream
+        self._fold_and_fr(lk_bits, True)
+        self._rc(gl.dev_riss_convert_parties(self.sums, n, t, B, self.r_q, 0, stream=st), "hbmpc_gl_dev_riss_convert_parties")
+        self._rc(gl.dev_fr_op("add", self.r_q, self.b_q, n * B, self.rb, st), "r + b")
+        self._rc(gl.dev_vandermonde_apply_parties(self.rb, self.G, n, t, n, self.Y, st), "open: encode")
+
+    def finish(self):
+        self.open()
+        self._rc(self.fr.dev_prandbit_finalize_parties(self.opened, self.r_p, self.r_2, self.B, self.n, self.b_p, self.b_2, self.stream),
+                 "hbmpc_dev_prandbit_finalize_parties")
+
+    def run(self, lk_bits):
+        self.prepare(lk_bits)
+        self.finish()
+
+    def open_summary(self):
+        """(n_fallback, n_failed, first_failed, first_error) of the two decodes of the open"""
+        return [tuple(int(v) for v in self.download_named(k, np.uint32, (4,))) for k in ("summary_first", "summary")]

@@ -254,6 +254,53 @@ impl GpuShares {
         self.check(rc, n)?;
         Ok(GpuPipeline { gpu: self, pipe, owned: true })
     }
+    // ---- PRandBit / PRandInt (fpmul/prandbitd.rs): device pointers in, device pointers out; `u64` values are folded r_T or Goldilocks elements
+    /// the maximal unqualified sets in the order the conversion indexes them: `(0..n).combinations(t)` (prandbitd.rs:479)
+    pub fn riss_tsets(n: usize, t: usize) -> Option<Vec<Vec<usize>>> {
+        let mut count = 0usize;
+        if unsafe { sys::hbmpc_riss_tsets(n, t, std::ptr::null_mut(), &mut count) } != sys::ShareSuccess {
+            return None;
+        }
+        let mut ids = vec![0usize; count * t];
+        if unsafe { sys::hbmpc_riss_tsets(n, t, ids.as_mut_ptr(), &mut count) } != sys::ShareSuccess {
+            return None;
+        }
+        Some(if t == 0 { vec![Vec::new(); count] } else { ids.chunks(t).map(|c| c.to_vec()).collect() })
+    }
+    /// the fold of prandbitd.rs:667-684 with the bound test of :638-647: contrib [n][sets][batch] -> sums [sets][batch], bad [n][sets] bytes
+    /// (the caller drops or re-requests the sets with a verdict, where the reference answers `PRandError::InvalidMessage`).
+    /// `Err(true)`: `PRandError::SurpassedFieldCapacity` (prandbitd.rs:506-517); `Err(false)`: any other failure (`last_error`)
+    #[allow(clippy::too_many_arguments)]
+    pub fn riss_fold_dev(&self, contrib: *const u64, n: usize, sets: usize, batch: usize, l_plus_k: usize, sums: *mut u64, bad: *mut u8,
+                         stream: *mut core::ffi::c_void) -> Result<(), bool> {
+        match unsafe { sys::hbmpc_dev_riss_fold(self.ctx, contrib, n, sets, batch, l_plus_k, sums, bad, stream) } {
+            sys::ShareSuccess => Ok(()),
+            sys::HBMPC_FIELD_CAPACITY => Err(true),
+            _ => Err(false),
+        }
+    }
+    /// the heavy step of `try_advance_from_riss` (prandbitd.rs:311-356) for this node: r over the party's own sets -> its share in this
+    /// context's field (`out`: one U256 or one u64 per element) and, when `share_2` is not null, its GF(2^8) share
+    #[allow(clippy::too_many_arguments)]
+    pub fn riss_convert_own_dev(&self, r: *const u64, n: usize, t: usize, batch: usize, party: usize, out: *mut core::ffi::c_void, share_2: *mut u8,
+                                goldilocks: bool, stream: *mut core::ffi::c_void) -> Result<(), InterpolateError> {
+        let ids = [party];
+        let rc = unsafe {
+            if goldilocks {
+                sys::hbmpc_gl_dev_riss_convert_parties(self.ctx, r, n, t, batch, ids.as_ptr(), 1, 1, out as *mut u64, share_2, stream)
+            } else {
+                sys::hbmpc_dev_riss_convert_parties(self.ctx, r, n, t, batch, ids.as_ptr(), 1, 1, out as *mut sys::U256, share_2, stream)
+            }
+        };
+        self.check(rc, n)
+    }
+    /// the arithmetic of `try_finalize_bit` (prandbitd.rs:189-211) for `parties` parties: b_p = G(v) - r_p, b_2 = r_2 + lsb(v)
+    #[allow(clippy::too_many_arguments)]
+    pub fn prandbit_finalize_dev(&self, opened: *const u64, r_p: *const sys::U256, r_2: *const u8, batch: usize, parties: usize, b_p: *mut sys::U256,
+                                 b_2: *mut u8, stream: *mut core::ffi::c_void) -> Result<(), InterpolateError> {
+        let rc = unsafe { sys::hbmpc_dev_prandbit_finalize_parties(self.ctx, opened, r_p, r_2, batch, parties, b_p, b_2, stream) };
+        self.check(rc, parties)
+    }
     /// `TripleGenNode::init_batch` + BatchRecon(2t) + finalize for all n parties (triple_gen/triple_generation.rs:304-364,164-232)
     pub fn pipe_triplegen(&self, n: usize, t: usize, triples: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
         let mut p = std::ptr::null_mut();
