@@ -108,7 +108,7 @@ static ShareErrorCode riss_convert_any(hbmpc_ctx* ctx, const uint64_t* r, size_t
     // waves' reads of r hit the cache, and 16 parties per workgroup leave one wave per SIMD).  With only a few sets there is nothing to
     // slice: Goldilocks then takes the 16-party form (n = 4, t = 1, 2^20 elements: 0.038 ms against 0.072 ms; DESIGN.md section 4).
     const bool wide = ctx->riss_form == 1 || (ctx->riss_form == 0 && parties > 1 && ctx->impl == IMPL_GOLD && Tn < 64);
-    launch_riss_convert(ctx->impl, wide, r, B, (unsigned)Tn, tab, cols, (unsigned)parties, WO(out), out2, s);
+    launch_riss_convert(ctx->impl, wide, r, B, (unsigned)Tn, tab, cols, (unsigned)parties, as_words(out), out2, s);
     HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
@@ -131,7 +131,7 @@ extern "C" ShareErrorCode hbmpc_dev_prandbit_finalize_parties(hbmpc_ctx* ctx, co
     if (!opened || !r_p || !r_2 || !bp_out || !b2_out) return fail(ctx, InvalidInput, "null buffer");
     if ((B + 255) / 256 > 0x7fffffffu) return fail(ctx, InvalidInput, "B beyond the supported range");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    launch_prandbit_finalize(ctx->impl, opened, W(r_p), r_2, B, (unsigned)parties, WO(bp_out), b2_out, pick(ctx, stream));
+    launch_prandbit_finalize(ctx->impl, opened, as_words(r_p), r_2, B, (unsigned)parties, as_words(bp_out), b2_out, pick(ctx, stream));
     HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }

@@ -1,6 +1,6 @@
 // hbmpc_capi.hip -- the C ABI of include/hbmpc_hip.h: context, table cache, kernel dispatch.
-// There is no CPU data path here: host code only validates arguments, builds the small constant
-// tables (tables.hpp) and launches kernels.
+// There is no CPU data path here and no device code either: host code validates arguments, builds the small constant
+// tables (tables.hpp) and calls the launchers of launchers.hpp (the kernels and their launches are in tu_*.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,7 +17,7 @@
 
 #include "../../include/hbmpc_hip.h"
 #include "fr_gold.hpp"
-#include "kernels_elem.hpp"
+#include "elem_args.hpp"
 #include "kernels_fpmul_wave.hpp"
 #include "kernels_triplegen_wg.hpp"
 #include "launchers.hpp"
@@ -28,9 +28,7 @@
 #include "kernels_mfma_gl.hpp"
 #include "encode_route.hpp"
 #include "recover_route.hpp"
-#include "kernels_sqrt.hpp"
 #include "tables_sqrt.hpp"
-#include "kernels_riss.hpp"
 #include "tables_riss.hpp"
 
 using namespace hbmpc;
@@ -1214,77 +1212,24 @@ extern "C" ShareErrorCode hbmpc_gl_make_vandermonde(hbmpc_ctx* ctx, size_t n, si
 }
 
 // ---- element-wise ------------------------------------------------------------------------------
+// (the launchers of tu_elem.hip size the grid: a lane per element)
 #define ELEM_PROLOGUE                                                           \
     if (!ctx) return InvalidInput;                                              \
     if (N == 0) return ShareSuccess;                                            \
     HIP_TRY(ctx, hipSetDevice(ctx->device));                                    \
-    hipStream_t s = pick(ctx, stream);                                          \
-    const unsigned grid = (unsigned)((N + 255) / 256);                          \
-    (void)grid;
+    hipStream_t s = pick(ctx, stream);
 
-#define BY_IMPL(KERNEL, ...)                                                                         \
-    do {                                                                                             \
-        if (ctx->impl == IMPL_U29)                                                                   \
-            hipLaunchKernelGGL((KERNEL<U29>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);             \
-        else                                                                                         \
-            hipLaunchKernelGGL((KERNEL<Sat32>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);           \
-        HIP_TRY(ctx, hipGetLastError());                                                             \
-    } while (0)
-
-// the same with dim3(grid, P): party-batched kernels (blockIdx.y = party)
-#define BY_FIELD_P(P, KERNEL, ...)                                                                   \
-    do {                                                                                             \
-        const dim3 gp(grid, (unsigned)(P));                                                          \
-        if (ctx->impl == IMPL_U29)                                                                   \
-            hipLaunchKernelGGL((KERNEL<U29>), gp, dim3(256), 0, s, __VA_ARGS__);                     \
-        else if (ctx->impl == IMPL_SAT32)                                                            \
-            hipLaunchKernelGGL((KERNEL<Sat32>), gp, dim3(256), 0, s, __VA_ARGS__);                   \
-        else                                                                                         \
-            hipLaunchKernelGGL((KERNEL<Gold>), gp, dim3(256), 0, s, __VA_ARGS__);                    \
-        HIP_TRY(ctx, hipGetLastError());                                                             \
-    } while (0)
-#define BY_IMPL_P(P, KERNEL, ...)                                                                    \
-    do {                                                                                             \
-        const dim3 gp(grid, (unsigned)(P));                                                          \
-        if (ctx->impl == IMPL_U29)                                                                   \
-            hipLaunchKernelGGL((KERNEL<U29>), gp, dim3(256), 0, s, __VA_ARGS__);                     \
-        else                                                                                         \
-            hipLaunchKernelGGL((KERNEL<Sat32>), gp, dim3(256), 0, s, __VA_ARGS__);                   \
-        HIP_TRY(ctx, hipGetLastError());                                                             \
-    } while (0)
 #define CHECK_PARTIES(P) do { if ((P) == 0 || (P) > 65535) return fail(ctx, InvalidInput, "parties must be in 1..65535"); } while (0)
 
-#define BY_FIELD(KERNEL, ...)                                                                        \
-    do {                                                                                             \
-        if (ctx->impl == IMPL_U29)                                                                   \
-            hipLaunchKernelGGL((KERNEL<U29>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);             \
-        else if (ctx->impl == IMPL_SAT32)                                                            \
-            hipLaunchKernelGGL((KERNEL<Sat32>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);           \
-        else                                                                                         \
-            hipLaunchKernelGGL((KERNEL<Gold>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);            \
-        HIP_TRY(ctx, hipGetLastError());                                                             \
-    } while (0)
-
-#define W(p) ((const uint32_t*)(p))
-#define WO(p) ((uint32_t*)(p))
+// device buffers of either field as the kernels' 32-bit words
+static const uint32_t* as_words(const void* p) { return (const uint32_t*)p; }
+static uint32_t* as_words(void* p) { return (uint32_t*)p; }
 
 static ShareErrorCode fr_op_any(hbmpc_ctx* ctx, int op, const void* a, const void* b, size_t N, void* out, void* stream) {
     ELEM_PROLOGUE
     if (op < 0 || op > 2) return fail(ctx, InvalidInput, "op must be 0 (add), 1 (sub) or 2 (mul)");
     const ElemConsts cs = elem_consts(ctx->impl);
-    if (ctx->impl == IMPL_GOLD) {
-        if (op == 0) hipLaunchKernelGGL((k_binop<Gold, OP_ADD>), dim3(grid), dim3(256), 0, s, W(a), W(b), N, cs, WO(out));
-        if (op == 1) hipLaunchKernelGGL((k_binop<Gold, OP_SUB>), dim3(grid), dim3(256), 0, s, W(a), W(b), N, cs, WO(out));
-        if (op == 2) hipLaunchKernelGGL((k_binop<Gold, OP_MUL>), dim3(grid), dim3(256), 0, s, W(a), W(b), N, cs, WO(out));
-    } else if (ctx->impl == IMPL_U29) {
-        if (op == 0) hipLaunchKernelGGL((k_binop<U29, OP_ADD>), dim3(grid), dim3(256), 0, s, W(a), W(b), N, cs, WO(out));
-        if (op == 1) hipLaunchKernelGGL((k_binop<U29, OP_SUB>), dim3(grid), dim3(256), 0, s, W(a), W(b), N, cs, WO(out));
-        if (op == 2) hipLaunchKernelGGL((k_binop<U29, OP_MUL>), dim3(grid), dim3(256), 0, s, W(a), W(b), N, cs, WO(out));
-    } else {
-        if (op == 0) hipLaunchKernelGGL((k_binop<Sat32, OP_ADD>), dim3(grid), dim3(256), 0, s, W(a), W(b), N, cs, WO(out));
-        if (op == 1) hipLaunchKernelGGL((k_binop<Sat32, OP_SUB>), dim3(grid), dim3(256), 0, s, W(a), W(b), N, cs, WO(out));
-        if (op == 2) hipLaunchKernelGGL((k_binop<Sat32, OP_MUL>), dim3(grid), dim3(256), 0, s, W(a), W(b), N, cs, WO(out));
-    }
+    launch_binop(ctx->impl, op, as_words(a), as_words(b), N, cs, as_words(out), s);
     HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
@@ -1306,17 +1251,7 @@ static ShareErrorCode fr_op_scalar_any(hbmpc_ctx* ctx, int op, const void* a, co
         if (HFr::geq(v)) return fail(ctx, InvalidInput, "scalar is not a canonical field element");
     }
     const ElemConsts cs = elem_consts(ctx->impl);
-#define SCALAR_OPS(F)                                                                                                       \
-    do {                                                                                                                    \
-        if (op == 0) hipLaunchKernelGGL((k_scalarop<F, OP_ADD>), dim3(grid), dim3(256), 0, s, W(a), sc, N, cs, WO(out));    \
-        if (op == 1) hipLaunchKernelGGL((k_scalarop<F, OP_SUB>), dim3(grid), dim3(256), 0, s, W(a), sc, N, cs, WO(out));    \
-        if (op == 2) hipLaunchKernelGGL((k_scalarop<F, OP_MUL>), dim3(grid), dim3(256), 0, s, W(a), sc, N, cs, WO(out));    \
-        if (op == 3) hipLaunchKernelGGL((k_scalarop<F, OP_RSUB>), dim3(grid), dim3(256), 0, s, W(a), sc, N, cs, WO(out));   \
-    } while (0)
-    if (ctx->impl == IMPL_GOLD) SCALAR_OPS(Gold);
-    else if (ctx->impl == IMPL_U29) SCALAR_OPS(U29);
-    else SCALAR_OPS(Sat32);
-#undef SCALAR_OPS
+    launch_scalarop(ctx->impl, op, as_words(a), sc, N, cs, as_words(out), s);
     HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
@@ -1324,7 +1259,8 @@ static ShareErrorCode triple_local_any(hbmpc_ctx* ctx, const void* a, const void
                                        void* stream) {
     ELEM_PROLOGUE
     const ElemConsts cs = elem_consts(ctx->impl);
-    BY_FIELD(k_triple_local, W(a), W(b), W(r2t), N, cs, WO(out));
+    launch_triple_local(ctx->impl, as_words(a), as_words(b), as_words(r2t), N, cs, as_words(out), s);
+    HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
 // TripleGenNode::init_batch for `parties` parties at once: x = a b - r2t per element, then the Vandermonde encode of the
@@ -1378,9 +1314,9 @@ static ShareErrorCode triple_encode_any(hbmpc_ctx* ctx, const void* a, const voi
                 return gold ? build_twiddles<HGl>(size, ctx->impl) : build_twiddles<HFr>(size, ctx->impl);
             }, &tw);
             if (rc != ShareSuccess) return rc;
-            const EvalOut out{WO(y), 0, (unsigned)parties};
-            if (gold ? launch_fft1_triple_gold(ilog2(size), (int)dp1, W(a), W(b), W(r2t), G, (int)n, tw, out, s)
-                     : launch_fft1_triple(ilog2(size), (int)dp1, W(a), W(b), W(r2t), G, (int)n, tw, out, elem_consts(ctx->impl).r2, s)) {
+            const EvalOut out{as_words(y), 0, (unsigned)parties};
+            if (gold ? launch_fft1_triple_gold(ilog2(size), (int)dp1, as_words(a), as_words(b), as_words(r2t), G, (int)n, tw, out, s)
+                     : launch_fft1_triple(ilog2(size), (int)dp1, as_words(a), as_words(b), as_words(r2t), G, (int)n, tw, out, elem_consts(ctx->impl).r2, s)) {
                 HIP_TRY(ctx, hipGetLastError());
                 return ShareSuccess;
             }
@@ -1396,20 +1332,23 @@ static ShareErrorCode triple_finalize_any(hbmpc_ctx* ctx, const void* rt, const 
                                           void* stream, size_t parties = 1) {
     ELEM_PROLOGUE
     CHECK_PARTIES(parties);
-    BY_FIELD_P(parties, k_triple_finalize, W(rt), W(opened), N, WO(c_out));
+    launch_triple_finalize(ctx->impl, as_words(rt), as_words(opened), N, (unsigned)parties, as_words(c_out), s);
+    HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
 static ShareErrorCode beaver_open_any(hbmpc_ctx* ctx, const void* a, const void* b, const void* x, const void* y, size_t N,
                                       void* d_sh, void* e_sh, void* stream) {
     ELEM_PROLOGUE
-    BY_FIELD(k_beaver_open, W(a), W(b), W(x), W(y), N, WO(d_sh), WO(e_sh));
+    launch_beaver_open(ctx->impl, as_words(a), as_words(b), as_words(x), as_words(y), N, as_words(d_sh), as_words(e_sh), s);
+    HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
 static ShareErrorCode beaver_open_pair_any(hbmpc_ctx* ctx, const void* a, const void* b, const void* x, const void* y, size_t N,
                                            size_t parties, void* de, void* stream) {
     ELEM_PROLOGUE
     CHECK_PARTIES(parties);
-    BY_FIELD_P(parties, k_beaver_open_pair, W(a), W(b), W(x), W(y), N, WO(de));
+    launch_beaver_open_pair(ctx->impl, as_words(a), as_words(b), as_words(x), as_words(y), N, (unsigned)parties, as_words(de), s);
+    HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
 static ShareErrorCode beaver_finalize_any(hbmpc_ctx* ctx, const void* c, const void* x, const void* y, const void* d,
@@ -1419,7 +1358,9 @@ static ShareErrorCode beaver_finalize_any(hbmpc_ctx* ctx, const void* c, const v
     const ElemConsts cs = elem_consts(ctx->impl);
     // the kernel loops over the parties (large N: the public operands are converted once per element) or spreads them
     // over gridDim.y (small N: latency)
-    BY_FIELD_P(N >= ((size_t)1 << 16) ? 1 : parties, k_beaver_finalize, W(c), W(x), W(y), W(d), W(e), N, cs, WO(z), (unsigned)parties);
+    const unsigned grid_parties = N >= ((size_t)1 << 16) ? 1 : (unsigned)parties;
+    launch_beaver_finalize(ctx->impl, as_words(c), as_words(x), as_words(y), as_words(d), as_words(e), N, cs, as_words(z), (unsigned)parties, grid_parties, s);
+    HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
 #define TYPED_PAIR(T, REQ, PFX)                                                                                          \
@@ -1518,8 +1459,8 @@ static ShareErrorCode sqrt_inverse_any(hbmpc_ctx* ctx, bool inverse, const void*
     SqrtTab t;
     const ShareErrorCode rc = sqrt_tab(ctx, &t);
     if (rc != ShareSuccess) return rc;
-    if (inverse) launch_inverse(ctx->impl, W(a), N, t, WO(out), flag, s);
-    else launch_sqrt(ctx->impl, W(a), N, t, WO(out), flag, s);
+    if (inverse) launch_inverse(ctx->impl, as_words(a), N, t, as_words(out), flag, s);
+    else launch_sqrt(ctx->impl, as_words(a), N, t, as_words(out), flag, s);
     HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
@@ -1537,7 +1478,7 @@ static ShareErrorCode randbit_finalize_any(hbmpc_ctx* ctx, const void* a, const 
     HIP_TRY(ctx, hipMemsetAsync(summary, 0xff, 8, s));  // first = all ones
     HIP_TRY(ctx, hipMemsetAsync((char*)summary + 8, 0, 8, s));
     if (N == 0) return ShareSuccess;
-    launch_randbit_finalize(ctx->impl, W(a), W(sq), N, (unsigned)parties, t, WO(out), status, reinterpret_cast<RandBitSummaryDev*>(summary), s);
+    launch_randbit_finalize(ctx->impl, as_words(a), as_words(sq), N, (unsigned)parties, t, as_words(out), status, reinterpret_cast<RandBitSummaryDev*>(summary), s);
     HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
@@ -1596,7 +1537,8 @@ static ShareErrorCode truncpr_rdash_impl(hbmpc_ctx* ctx, const U256* r_bits, siz
     const int impl = ctx->impl;
     ShareErrorCode rc = get_table(ctx, key("pow2", {m}, impl), [&] { return build_pow2(m, impl); }, &pow2);
     if (rc != ShareSuccess) return rc;
-    BY_IMPL_P(parties, k_truncpr_rdash, W(r_bits), (int)m, N, pow2, WO(r_dash));
+    launch_truncpr_rdash(impl, as_words(r_bits), (int)m, N, (unsigned)parties, pow2, as_words(r_dash), s);
+    HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
 extern "C" ShareErrorCode hbmpc_dev_truncpr_rdash(hbmpc_ctx* ctx, const U256* r_bits, size_t m, size_t N,
@@ -1616,7 +1558,8 @@ extern "C" ShareErrorCode hbmpc_dev_truncpr_open_share(hbmpc_ctx* ctx, const U25
     const HFr two = HFr::from_u64(2);
     const HFr p2m = two.pow_u64(m), p2k = two.pow_u64(k - 1);
     const ElemConsts cs = elem_consts(ctx->impl, &p2m, &p2k);
-    BY_IMPL(k_truncpr_open, W(a), W(r_dash), W(r_int), N, cs, WO(open_out));
+    launch_truncpr_open(ctx->impl, as_words(a), as_words(r_dash), as_words(r_int), N, cs, as_words(open_out), s);
+    HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
 extern "C" ShareErrorCode hbmpc_dev_fpmul_middle(hbmpc_ctx* ctx, const U256* c, const U256* x, const U256* y, const U256* d,
@@ -1635,8 +1578,10 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_middle(hbmpc_ctx* ctx, const U256* c, 
     const HFr two = HFr::from_u64(2);
     const HFr p2m = two.pow_u64(m), p2k = two.pow_u64(k - 1);
     const ElemConsts cs = elem_consts(impl, &p2m, &p2k);
-    BY_IMPL_P(N >= ((size_t)1 << 16) ? 1 : parties, k_fpmul_middle, W(c), W(x), W(y), W(d), W(e), W(r_bits), W(r_int), (int)m, N, cs, pow2,
-              WO(z_out), WO(r_dash_out), WO(open_out), (unsigned)parties);
+    const unsigned grid_parties = N >= ((size_t)1 << 16) ? 1 : (unsigned)parties;  // k_beaver_finalize's rule
+    launch_fpmul_middle(impl, as_words(c), as_words(x), as_words(y), as_words(d), as_words(e), as_words(r_bits), as_words(r_int), (int)m, N, cs, pow2,
+                        as_words(z_out), as_words(r_dash_out), as_words(open_out), (unsigned)parties, grid_parties, s);
+    HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
 static ShareErrorCode truncpr_finalize_impl(hbmpc_ctx* ctx, const U256* a, const U256* r_dash, const U256* c_open, size_t m,
@@ -1648,7 +1593,8 @@ static ShareErrorCode truncpr_finalize_impl(hbmpc_ctx* ctx, const U256* a, const
     CHECK_PARTIES(parties);
     const HFr inv = inv_pow2(ctx, m);
     const ElemConsts cs = elem_consts(ctx->impl, &inv);
-    BY_IMPL_P(parties, k_truncpr_finalize, W(a), W(r_dash), W(c_open), (int)(m > 256 ? 256 : m), N, cs, WO(d_out));
+    launch_truncpr_finalize(ctx->impl, as_words(a), as_words(r_dash), as_words(c_open), (int)(m > 256 ? 256 : m), N, (unsigned)parties, cs, as_words(d_out), s);
+    HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
 extern "C" ShareErrorCode hbmpc_dev_truncpr_finalize(hbmpc_ctx* ctx, const U256* a, const U256* r_dash,
@@ -1668,7 +1614,8 @@ extern "C" ShareErrorCode hbmpc_dev_modmul_ubench(hbmpc_ctx* ctx, U256* out_dev,
     ELEM_PROLOGUE
     if (threads % 256) return fail(ctx, InvalidInput, "threads must be a multiple of 256");
     const ElemConsts cs = elem_consts(ctx->impl);
-    BY_IMPL(k_modmul_ubench, WO(out_dev), iters, cs);
+    launch_modmul_ubench(ctx->impl, as_words(out_dev), threads, iters, cs, s);
+    HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }
 
@@ -1676,7 +1623,7 @@ extern "C" ShareErrorCode hbmpc_dev_traffic_ubench(hbmpc_ctx* ctx, const U256* x
     REQ_FR(ctx);
     if (!x_dev || !y_dev || G == 0 || m == 0 || n == 0 || m > 64 || n > 256) return fail(ctx, InvalidInput, "null buffer or shape out of range");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_traffic_ubench, dim3((unsigned)ctx->n_cus), dim3(768), 0, pick(ctx, stream), (const uint4*)x_dev, G, (int)m, (uint4*)y_dev, (int)n);
+    launch_traffic_ubench((unsigned)ctx->n_cus, (const uint4*)x_dev, G, (int)m, (uint4*)y_dev, (int)n, pick(ctx, stream));
     HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }

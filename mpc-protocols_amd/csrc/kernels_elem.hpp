@@ -2,17 +2,11 @@
 // One lane per element, 32-byte coalesced loads/stores; all of these are HBM-bound.
 // Data x data products need Montgomery form on one side: mont(mont(a, R^2), b) = a*b.
 #pragma once
+#include "elem_args.hpp"
 #include "fr_sat.hpp"
 #include "fr_u29.hpp"
 
 namespace hbmpc {
-
-// device-constant-form scalars every element-wise kernel may need
-struct ElemConsts {
-    uint32_t r2[9];     // R^2 mod r  (mont(x, r2) = x*R: canonical -> Montgomery)
-    uint32_t c0[9];     // kernel-specific constant 0 (e.g. 2^m, (2^m)^-1) in device-constant form
-    uint32_t c1[9];     // kernel-specific constant 1 (e.g. 2^(k-1) as a canonical element in limb form)
-};
 
 // Party-batched launches have gridDim.y = parties; per-party arrays are [party][N] (index ip), public operands -- the
 // opened values every party shares -- are [N] (index i).  Blocks are dispatched x-fastest, so the linear block id is
@@ -86,9 +80,6 @@ __global__ __launch_bounds__(256) void k_binop(const uint32_t* __restrict__ a, c
 // share (+,-,*) ONE field element, and element - share (common/mod.rs:205-280: Add<F>, Sub<F>, Mul<F>,
 // from_scalar_sub): the scalar travels in the kernel arguments, nobody materialises N copies of it
 enum { OP_RSUB = 3 };
-struct ScalarArg {
-    alignas(16) uint32_t w[8];  // canonical element (Goldilocks: the first two words)
-};
 template <class F, int OP>
 __global__ __launch_bounds__(256) void k_scalarop(const uint32_t* __restrict__ a, ScalarArg sc, size_t N, ElemConsts cs,
                                                   uint32_t* __restrict__ out) {

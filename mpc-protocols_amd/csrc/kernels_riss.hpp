@@ -21,18 +21,9 @@
 #include "fr_gold.hpp"
 #include "fr_sat.hpp"
 #include "fr_u29.hpp"
+#include "riss_args.hpp"
 
 namespace hbmpc {
-
-constexpr unsigned RISS_MAX_TSETS = 8192;  // C(n, t) of a supported shape (the accumulator bound above rests on it)
-
-// one (context, n, t[, own party]) coefficient table (tables_riss.hpp lays it out; every pointer is inside one cached table)
-struct RissTab {
-    const uint32_t* coef;   // [Tn][ncols][NC]: f_T(alpha_col) as a canonical integer, NC = 8 words (Fr) or 2 (Goldilocks); zero when col is in T
-    const uint32_t* coef2;  // [Tn][ncols]: f2_T(3^col) in GF(2^8), a word each (scalar loads); NULL when n > 255
-    const uint32_t* red;    // Fr: 1 and 2^224 in device-constant form, [2][NL]
-    unsigned ncols;
-};
 
 template <class F>
 HB_DEV typename F::E riss_from_words(const uint32_t w[8]) {
@@ -350,14 +341,4 @@ __global__ __launch_bounds__(256) void k_prandbit_finalize(const uint64_t* __res
     F::store_loose(bp + o * F::EW, F::template sub<2>(riss_from_words<F>(w), F::load(r_p + o * F::EW)));
     b2[o] = r_2[o] ^ (uint8_t)(x & 1u);
 }
-
-// tu_riss.hip
-void launch_riss_fold(const uint64_t* contrib, unsigned n, size_t Tn, size_t B, uint64_t bound, uint64_t* sums, uint8_t* bad, hipStream_t s);
-// wide: one workgroup per 64 elements and 16 parties; otherwise one per 64 elements and party, the sets in four slices (the caller
-// picks by measurement: capi_riss.inc)
-void launch_riss_convert(int impl, bool wide, const uint64_t* r, size_t B, unsigned Tn, const RissTab& tab, const uint32_t* cols, unsigned parties,
-                         uint32_t* out, uint8_t* out2, hipStream_t s);
-void launch_prandbit_finalize(int impl, const uint64_t* v, const uint32_t* r_p, const uint8_t* r_2, size_t N, unsigned parties, uint32_t* bp,
-                              uint8_t* b2, hipStream_t s);
-
 }  // namespace hbmpc

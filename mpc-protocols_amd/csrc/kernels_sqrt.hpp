@@ -17,31 +17,10 @@
 #include "fr_gold.hpp"
 #include "fr_sat.hpp"
 #include "fr_u29.hpp"
+#include "sqrt_args.hpp"
 
 namespace hbmpc {
 
-// one context's constants (tables_sqrt.hpp lays them out; every pointer is inside one table)
-struct SqrtTab {
-    const uint32_t* negw;   // [3][256][NL]: omega^(-j 2^(8m)), device-constant form
-    const uint32_t* posw;   // [4][256][NL]: omega^(j 2^(8m))
-    const uint32_t* r2;     // [NL] R^2 (canonical data -> Montgomery form)
-    const uint32_t* one_p;  // [NL] 1 in plain limb form (Montgomery form -> canonical data)
-    const uint32_t* half;   // [NL] 2^-1, device-constant form
-    const uint32_t* half_p; // [NL] 2^-1 in plain limb form
-    const uint32_t* e_sqrt; // (T-1)/2, 8 words, least significant first
-    const uint32_t* e_inv;  // p - 2
-    const uint8_t* keyt;    // [1 << kbits]: key of omega^(j 2^24) -> j
-    int bits_sqrt, bits_inv;
-    uint32_t kshift, kmask;
-};
-
-// RandBit's verdict (include/hbmpc_hip.h hbmpc_randbit_summary): the 64-bit minimum of (status << 32) | index -- a zero square
-// (status 1) ranks before a missing root (status 2), as ZeroSquare is checked over the whole batch first -- and the count
-struct RandBitSummaryDev {
-    unsigned long long first;
-    uint32_t n_failed;
-    uint32_t reserved;
-};
 enum { RB_OK = 0, RB_ZERO = 1, RB_NO_ROOT = 2 };
 
 template <class F>
@@ -62,8 +41,7 @@ HB_DEV typename F::E pow_fixed(const typename F::E& x, const uint32_t* __restric
     }
     return acc;
 }
-// the look-up key: a multiplicative hash of the two low limbs (Goldilocks' subgroup elements repeat in either 32-bit half)
-constexpr uint64_t SQRT_KEY_MUL = 0x9E3779B97F4A7C15ull;
+// the look-up key: a multiplicative hash (SQRT_KEY_MUL, sqrt_args.hpp) of the two low limbs (Goldilocks' subgroup elements repeat in either 32-bit half)
 template <class F>
 HB_DEV uint32_t sqrt_key(const SqrtTab& t, const typename F::E& x) {
     const uint64_t w = ((uint64_t)x.l[1] << 32) | x.l[0];
@@ -202,11 +180,4 @@ __global__ __launch_bounds__(256) void k_randbit_finalize(const uint32_t* __rest
         F::store_loose(out + ip * F::EW, F::add(v, hp));
     }
 }
-
-// tu_sqrt.hip
-void launch_sqrt(int impl, const uint32_t* a, size_t N, const SqrtTab& t, uint32_t* root, uint8_t* has_root, hipStream_t s);
-void launch_inverse(int impl, const uint32_t* a, size_t N, const SqrtTab& t, uint32_t* inv, uint8_t* ok, hipStream_t s);
-void launch_randbit_finalize(int impl, const uint32_t* a, const uint32_t* sq, size_t N, unsigned parties, const SqrtTab& t, uint32_t* out,
-                             uint8_t* status, RandBitSummaryDev* summary, hipStream_t s);
-
 }  // namespace hbmpc

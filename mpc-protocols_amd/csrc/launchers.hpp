@@ -1,6 +1,7 @@
-// launchers.hpp -- the kernel instantiations live in several translation units (tu_*.hip) so that
-// they compile in parallel; these are their entry points.  Each returns false when the requested
-// shape is not one it instantiates.
+// launchers.hpp -- every kernel instantiation and every launch lives in a translation unit of its own kind (tu_*.hip), so
+// that they compile in parallel and the C ABI files (hbmpc_capi.hip, capi_*.inc, capi_pipelines.hip) hold host code only; these
+// are their entry points.  A bool one returns false when the requested shape is not one it instantiates.  Where a launcher
+// takes `impl` (FieldImpl), the field type is picked by by_field / by_fr_impl of field_dispatch.hpp and nowhere else.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -68,7 +69,7 @@ bool launch_gold_fft1(int log, int cnt, const uint32_t* x, size_t G, int n, cons
 bool launch_gold_fftP(int dp1, const uint32_t* x, size_t G, int n, int P, const uint32_t* tw16, const uint32_t* twist,
                       EvalOut y, hipStream_t s);
 bool launch_gold_recover(int m, bool p0, const RecoverArgs& ra, unsigned grid, hipStream_t s);
-// generic Horner evaluation (impl: 0 = U29, 1 = Sat32, 2 = Goldilocks)
+// generic Horner evaluation
 void launch_eval_generic(int impl, const uint32_t* x, size_t G, int n, int dp1, const uint32_t* alpha, EvalOut y,
                          hipStream_t s);
 // batch recover, U29, register-resident m <= 16 (launch_recover tries the four translation units)
@@ -157,5 +158,47 @@ bool launch_fft1_mix_lo(int log, int cnt, const uint32_t* x, size_t xs, size_t G
 bool launch_gold_fft1_mix(int log, int cnt, const uint32_t* x, size_t xs, size_t G, int n, const uint32_t* tw, const MixOut& o, hipStream_t s);
 void launch_rows_party_major(int ew64, const uint64_t* src, size_t G, size_t K, int row0, int rows, int nother, uint64_t* dst, hipStream_t s);
 void launch_take_c0(int ew64, const uint64_t* coeffs, size_t G, int m, uint64_t* c0, hipStream_t s);
+
+// element-wise share arithmetic (tu_elem.hip, kernels_elem.hpp): a lane per element; `parties` > 1: [party][N] operands, the
+// party in blockIdx.y.  grid_parties of the two kernels that loop over the parties themselves: 1 or `parties` (the caller picks by N)
+struct ElemConsts;
+struct ScalarArg;
+void launch_binop(int impl, int op, const uint32_t* a, const uint32_t* b, size_t N, const ElemConsts& cs, uint32_t* out, hipStream_t s);
+void launch_scalarop(int impl, int op, const uint32_t* a, const ScalarArg& sc, size_t N, const ElemConsts& cs, uint32_t* out, hipStream_t s);
+void launch_triple_local(int impl, const uint32_t* a, const uint32_t* b, const uint32_t* r2t, size_t N, const ElemConsts& cs, uint32_t* out, hipStream_t s);
+void launch_triple_finalize(int impl, const uint32_t* rt, const uint32_t* opened, size_t N, unsigned parties, uint32_t* c_out, hipStream_t s);
+void launch_beaver_open(int impl, const uint32_t* a, const uint32_t* b, const uint32_t* x, const uint32_t* y, size_t N, uint32_t* d_sh, uint32_t* e_sh,
+                        hipStream_t s);
+void launch_beaver_open_pair(int impl, const uint32_t* a, const uint32_t* b, const uint32_t* x, const uint32_t* y, size_t N, unsigned parties, uint32_t* de,
+                             hipStream_t s);
+void launch_beaver_finalize(int impl, const uint32_t* c, const uint32_t* x, const uint32_t* y, const uint32_t* d, const uint32_t* e, size_t N,
+                            const ElemConsts& cs, uint32_t* z, unsigned parties, unsigned grid_parties, hipStream_t s);
+// Fr only (by_fr_impl)
+void launch_truncpr_rdash(int impl, const uint32_t* r_bits, int m, size_t N, unsigned parties, const uint32_t* pow2, uint32_t* r_dash, hipStream_t s);
+void launch_truncpr_open(int impl, const uint32_t* a, const uint32_t* r_dash, const uint32_t* r_int, size_t N, const ElemConsts& cs, uint32_t* open_out,
+                         hipStream_t s);
+void launch_fpmul_middle(int impl, const uint32_t* c, const uint32_t* x, const uint32_t* y, const uint32_t* d, const uint32_t* e, const uint32_t* r_bits,
+                         const uint32_t* r_int, int m, size_t N, const ElemConsts& cs, const uint32_t* pow2, uint32_t* z, uint32_t* r_dash,
+                         uint32_t* open_out, unsigned parties, unsigned grid_parties, hipStream_t s);
+void launch_truncpr_finalize(int impl, const uint32_t* a, const uint32_t* r_dash, const uint32_t* c_open, int m, size_t N, unsigned parties,
+                             const ElemConsts& cs, uint32_t* d_out, hipStream_t s);
+void launch_modmul_ubench(int impl, uint32_t* out, size_t threads, uint32_t iters, const ElemConsts& cs, hipStream_t s);
+void launch_traffic_ubench(unsigned wgs, const uint4* x, size_t G, int m, uint4* y, int n, hipStream_t s);
+// square roots, inverses, RandBit's last step (tu_sqrt.hip, kernels_sqrt.hpp)
+struct SqrtTab;
+struct RandBitSummaryDev;
+void launch_sqrt(int impl, const uint32_t* a, size_t N, const SqrtTab& t, uint32_t* root, uint8_t* has_root, hipStream_t s);
+void launch_inverse(int impl, const uint32_t* a, size_t N, const SqrtTab& t, uint32_t* inv, uint8_t* ok, hipStream_t s);
+void launch_randbit_finalize(int impl, const uint32_t* a, const uint32_t* sq, size_t N, unsigned parties, const SqrtTab& t, uint32_t* out,
+                             uint8_t* status, RandBitSummaryDev* summary, hipStream_t s);
+// PRandBit / PRandInt (tu_riss.hip, kernels_riss.hpp)
+struct RissTab;
+void launch_riss_fold(const uint64_t* contrib, unsigned n, size_t Tn, size_t B, uint64_t bound, uint64_t* sums, uint8_t* bad, hipStream_t s);
+// wide: one workgroup per 64 elements and 16 parties; otherwise one per 64 elements and party, the sets in four slices (the caller
+// picks by measurement: capi_riss.inc)
+void launch_riss_convert(int impl, bool wide, const uint64_t* r, size_t B, unsigned Tn, const RissTab& tab, const uint32_t* cols, unsigned parties,
+                         uint32_t* out, uint8_t* out2, hipStream_t s);
+void launch_prandbit_finalize(int impl, const uint64_t* v, const uint32_t* r_p, const uint8_t* r_2, size_t N, unsigned parties, uint32_t* bp,
+                              uint8_t* b2, hipStream_t s);  // Fr only
 
 }  // namespace hbmpc

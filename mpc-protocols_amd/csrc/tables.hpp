@@ -6,13 +6,10 @@
 #include <vector>
 
 #include "../../include/hbmpc_hip.h"
+#include "field_dispatch.hpp"  // FieldImpl, impl_nl, impl_ebytes
 #include "host_fr.hpp"
 
 namespace hbmpc {
-
-enum FieldImpl { IMPL_U29 = 0, IMPL_SAT32 = 1, IMPL_GOLD = 2 };
-inline int impl_nl(int impl) { return impl == IMPL_U29 ? 9 : impl == IMPL_SAT32 ? 8 : 2; }
-inline size_t impl_ebytes(int impl) { return impl == IMPL_GOLD ? 8 : 32; }  // bytes per stored element
 
 inline void put_const(std::vector<uint32_t>& out, const HFr& v, int impl) {
     uint32_t tmp[9];

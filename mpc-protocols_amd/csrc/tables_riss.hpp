@@ -6,7 +6,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "kernels_riss.hpp"
+#include "riss_args.hpp"
 #include "tables.hpp"
 
 namespace hbmpc {

@@ -5,7 +5,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "kernels_sqrt.hpp"
+#include "sqrt_args.hpp"
 #include "tables.hpp"
 
 namespace hbmpc {

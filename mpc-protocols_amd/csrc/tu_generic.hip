@@ -1,14 +1,19 @@
 #include <cstring>
+#include "field_dispatch.hpp"
 #include "fr_gold.hpp"
 #include "kernels_eval.hpp"
 #include "launchers.hpp"
 namespace hbmpc {
+// a run-time flag as a compile-time one: fn(std::true_type{}) or fn(std::false_type{})
+template <class Fn>
+static void by_bool(bool b, Fn&& fn) {
+    if (b) fn(std::true_type{});
+    else fn(std::false_type{});
+}
 void launch_eval_generic(int impl, const uint32_t* x, size_t G, int n, int dp1, const uint32_t* alpha, EvalOut y,
                          hipStream_t s) {
     const unsigned grid = (unsigned)((G + 255) / 256);
-    if (impl == 0) hipLaunchKernelGGL((k_eval_generic<U29>), dim3(grid, y.parties), dim3(256), 0, s, x, G, n, dp1, alpha, y.y, y.ys ? y.ys : G);
-    else if (impl == 1) hipLaunchKernelGGL((k_eval_generic<Sat32>), dim3(grid, y.parties), dim3(256), 0, s, x, G, n, dp1, alpha, y.y, y.ys ? y.ys : G);
-    else hipLaunchKernelGGL((k_eval_generic<Gold>), dim3(grid, y.parties), dim3(256), 0, s, x, G, n, dp1, alpha, y.y, y.ys ? y.ys : G);
+    by_field(impl, [&](auto f) { hipLaunchKernelGGL((k_eval_generic<field_t<decltype(f)>>), dim3(grid, y.parties), dim3(256), 0, s, x, G, n, dp1, alpha, y.y, y.ys ? y.ys : G); });
 }
 void launch_eval_wide_dot(const uint32_t* x, size_t G, int n, int dp1, const uint32_t* vmat, EvalOut y, hipStream_t s) {
     const unsigned grid = (unsigned)((G + 3) / 4);
@@ -18,26 +23,18 @@ void launch_eval_wide_dot(const uint32_t* x, size_t G, int n, int dp1, const uin
 }
 void launch_eval_wide(int impl, const uint32_t* x, size_t G, int n, int dp1, const uint32_t* alpha, EvalOut y, hipStream_t s) {
     const unsigned grid = (unsigned)((G + 3) / 4);
-    if (impl == 0) hipLaunchKernelGGL((k_eval_wide<U29>), dim3(grid, y.parties), dim3(256), 0, s, x, G, n, dp1, alpha, y.y, y.ys ? y.ys : G);
-    else if (impl == 1) hipLaunchKernelGGL((k_eval_wide<Sat32>), dim3(grid, y.parties), dim3(256), 0, s, x, G, n, dp1, alpha, y.y, y.ys ? y.ys : G);
-    else hipLaunchKernelGGL((k_eval_wide<Gold>), dim3(grid, y.parties), dim3(256), 0, s, x, G, n, dp1, alpha, y.y, y.ys ? y.ys : G);
+    by_field(impl, [&](auto f) { hipLaunchKernelGGL((k_eval_wide<field_t<decltype(f)>>), dim3(grid, y.parties), dim3(256), 0, s, x, G, n, dp1, alpha, y.y, y.ys ? y.ys : G); });
 }
 void launch_recover_generic(int impl, bool p0, const RecoverArgs& ra, unsigned grid, hipStream_t s) {
-    if (impl == 0) {
-        if (p0) hipLaunchKernelGGL((k_batch_recover_generic<U29, true>), dim3(grid), dim3(256), 0, s, ra);
-        else hipLaunchKernelGGL((k_batch_recover_generic<U29, false>), dim3(grid), dim3(256), 0, s, ra);
-    } else if (impl == 1) {
-        if (p0) hipLaunchKernelGGL((k_batch_recover_generic<Sat32, true>), dim3(grid), dim3(256), 0, s, ra);
-        else hipLaunchKernelGGL((k_batch_recover_generic<Sat32, false>), dim3(grid), dim3(256), 0, s, ra);
-    } else {
-        if (p0) hipLaunchKernelGGL((k_batch_recover_generic<Gold, true>), dim3(grid), dim3(256), 0, s, ra);
-        else hipLaunchKernelGGL((k_batch_recover_generic<Gold, false>), dim3(grid), dim3(256), 0, s, ra);
-    }
+    by_field(impl, [&](auto f) {
+        using F = typename decltype(f)::type;
+        by_bool(p0, [&](auto P0) { hipLaunchKernelGGL((k_batch_recover_generic<F, decltype(P0)::value>), dim3(grid), dim3(256), 0, s, ra); });
+    });
 }
 // LDS of one workgroup of k_batch_recover_wide; *tab_words = 0 when the call's table cannot be staged (not contiguous, or
 // beyond what a launch may ask for without raising the function's limit)
 static size_t wide_lds(int impl, const RecoverArgs& ra, bool p0, int ow_sel, int* tab_words, int* split) {
-    const size_t ew = impl == 2 ? 2 : 8, nl = impl == 0 ? 9 : impl == 1 ? 8 : 2;
+    const size_t ew = impl_ebytes(impl) / 4, nl = (size_t)impl_nl(impl);
     const size_t nv = (size_t)(ra.needed - ra.m), ow = p0 ? 1 : ow_sel ? (size_t)ow_sel : (size_t)ra.m;
     const size_t front = 4 * (size_t)ra.needed * ew * 4;
     const size_t tw = (nv + ow) * (size_t)ra.m * nl;
@@ -59,36 +56,23 @@ void launch_recover_wide(int impl, bool p0, const RecoverArgs& ra, const SecondA
     const size_t lds = wide_lds(impl, ra, p0, ow_sel, &wa.tab_words, &wa.split);
     const bool tab = wa.tab_words != 0;
     wa.lk = 0;
-    if (tab && impl == 0) {  // U29: a row's products shared by up to four lanes while every row still fits the wave (dot_shared)
+    if (tab && impl == IMPL_U29) {  // a row's products shared by up to four lanes while every row still fits the wave (dot_shared)
         const int rows = (ra.needed - ra.m) + (p0 ? 1 : ow_sel ? ow_sel : ra.m);
         while (wa.lk < 2 && (rows << (wa.lk + 1)) <= 64 && (2 << wa.lk) <= ra.m) ++wa.lk;
     }
-#define HBMPC_WIDE(F, P0) \
-    do { \
-        if (tab) hipLaunchKernelGGL((k_batch_recover_wide<F, P0, true>), dim3(grid), dim3(256), lds, s, wa); \
-        else hipLaunchKernelGGL((k_batch_recover_wide<F, P0, false>), dim3(grid), dim3(256), lds, s, wa); \
-    } while (0)
-    if (impl == 0) {
-        if (p0) HBMPC_WIDE(U29, true);
-        else HBMPC_WIDE(U29, false);
-    } else if (impl == 1) {
-        if (p0) HBMPC_WIDE(Sat32, true);
-        else HBMPC_WIDE(Sat32, false);
-    } else {
-        if (p0) HBMPC_WIDE(Gold, true);
-        else HBMPC_WIDE(Gold, false);
-    }
-#undef HBMPC_WIDE
+    by_field(impl, [&](auto f) {
+        using F = typename decltype(f)::type;
+        by_bool(p0, [&](auto P0) {
+            if (tab) hipLaunchKernelGGL((k_batch_recover_wide<F, decltype(P0)::value, true>), dim3(grid), dim3(256), lds, s, wa);
+            else hipLaunchKernelGGL((k_batch_recover_wide<F, decltype(P0)::value, false>), dim3(grid), dim3(256), lds, s, wa);
+        });
+    });
 }
 void launch_second_chance(int impl, const SecondArgs& a, unsigned grid, hipStream_t s) {
-    if (impl == 0) hipLaunchKernelGGL((k_second_chance<U29>), dim3(grid), dim3(256), 0, s, a);
-    else if (impl == 1) hipLaunchKernelGGL((k_second_chance<Sat32>), dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_second_chance<Gold>), dim3(grid), dim3(256), 0, s, a);
+    by_field(impl, [&](auto f) { hipLaunchKernelGGL((k_second_chance<field_t<decltype(f)>>), dim3(grid), dim3(256), 0, s, a); });
 }
 void launch_matvec(int impl, const uint32_t* lb, const uint32_t* y, int S, uint32_t* out, hipStream_t s) {
     const unsigned grid = (unsigned)((S + 255) / 256);
-    if (impl == 0) hipLaunchKernelGGL((k_matvec<U29>), dim3(grid), dim3(256), 0, s, lb, y, S, out);
-    else if (impl == 1) hipLaunchKernelGGL((k_matvec<Sat32>), dim3(grid), dim3(256), 0, s, lb, y, S, out);
-    else hipLaunchKernelGGL((k_matvec<Gold>), dim3(grid), dim3(256), 0, s, lb, y, S, out);
+    by_field(impl, [&](auto f) { hipLaunchKernelGGL((k_matvec<field_t<decltype(f)>>), dim3(grid), dim3(256), 0, s, lb, y, S, out); });
 }
 }

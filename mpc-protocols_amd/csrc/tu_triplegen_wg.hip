@@ -1,6 +1,7 @@
 // TripleGenNode for all parties of a small batch in one launch (kernels_triplegen_wg.hpp)
 #include <hip/hip_runtime.h>
 
+#include "field_dispatch.hpp"
 #include "fr_gold.hpp"
 #include "fr_u29.hpp"
 #include "kernels_triplegen_wg.hpp"
@@ -8,9 +9,13 @@
 
 namespace hbmpc {
 void launch_triplegen_wg(int impl, const TripleGenWgArgs& a, hipStream_t s) {
-    const bool gold = impl == 2;
-    const TripleGenWgLds L(a.n, a.t, gold ? 2 : 12, gold ? 2 : 9);
-    if (gold) hipLaunchKernelGGL((k_triplegen_wg<Gold>), dim3((unsigned)a.G), dim3(256), (size_t)L.total * 4, s, a);
-    else hipLaunchKernelGGL((k_triplegen_wg<U29>), dim3((unsigned)a.G), dim3(256), (size_t)L.total * 4, s, a);
+    by_field(impl, [&](auto f) {
+        using F = typename decltype(f)::type;
+        // the kernel exists over U29 and Goldilocks; the caller sends a Sat32 context down the four-launch path
+        if constexpr (!std::is_same<F, Sat32>::value) {
+            const TripleGenWgLds L(a.n, a.t, F::NL == 9 ? 12 : F::NL, F::NL);  // the kernel's own LS, NL
+            hipLaunchKernelGGL((k_triplegen_wg<F>), dim3((unsigned)a.G), dim3(256), (size_t)L.total * 4, s, a);
+        }
+    });
 }
 }  // namespace hbmpc
