@@ -199,6 +199,7 @@ void hbmpc_graph_destroy(hbmpc_graph* graph);
  * block owned by the handle and is reached by name (hbmpc_pipe_buffer; elements of the context's field, [party][...] layouts):
  *   triplegen      a, b, r2t, rt (inputs [n][N]); c (output [n][N]); Y, Z, opened, status, summary
  *   fpmul          x, y, ta, tb, tc, rint ([n][N]), rbits ([n][m][N]) (inputs); out ([n][N]); z, rdash, osh, desh, dop, eop, cop
+ *   truncpr        a, rint, rbits (inputs; w with a multiplier); out; c, rdash, osh, cop, status, summary (see its create call)
  *   ransha         coeffs ([dealer][K][t+1], column 0 the secret); S ([dealer][recipient][K]); y; out ([party][K][n-2t]); bad
  *   randousha      coeffs_t, coeffs_2t; S_t, S_2t; y_t, y_2t; out_t, out_2t ([party][K][t+1]); bad
  *   preprocessing  its parts by name (hbmpc_pipe_part: "ransha", "randousha", "triplegen"; borrowed handles)
@@ -212,6 +213,13 @@ typedef struct hbmpc_pipe hbmpc_pipe;
 ShareErrorCode hbmpc_pipe_triplegen_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream, hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_fpmul_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t k, size_t m, size_t open_senders,
                                        void* stream, hbmpc_pipe** pipe_out);
+/* TruncPr (fpmul/truncpr.rs:185-318) of N values for n parties, and with_multiplier != 0 FPDivConst (fpdiv/fpdiv_const.rs:61-99):
+ * FPDivConstNode for fixed-point values of k_fixed bits with f fractional bits is this handle with k = 2 k_fixed, m = f and the
+ * multipliers hbmpc_fixed_point_reciprocal_scaled makes of the denominators uploaded as w.  run() is hbmpc_dev_truncpr_parties.
+ * Buffers: a, rint ([n][N]), rbits ([n][m][N]) (inputs); w ([N], public) and c ([n][N] = a * w) only with a multiplier; out
+ * ([n][N]); rdash, osh ([n][N]); cop ([N]); status ([N] bytes); summary.  TypeMismatch on a Goldilocks context. */
+ShareErrorCode hbmpc_pipe_truncpr_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t k, size_t m, size_t open_senders,
+                                         int with_multiplier, void* stream, hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_ransha_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t K, size_t verify_senders, void* stream,
                                         hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_randousha_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t K, void* stream, hbmpc_pipe** pipe_out);
@@ -558,6 +566,33 @@ ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* sender_ids,
                                        size_t n, size_t t, U256* de_sh_ws, U256* de_out, U256* z_out, U256* r_dash_out, U256* open_sh_out,
                                        U256* c_open_out, U256* d_out, uint8_t* status_out, hbmpc_recover_summary* summary_first_dev,
                                        hbmpc_recover_summary* summary_dev, void* stream);
+/* TruncPrNode on its own for every party of this device (fpmul/truncpr.rs:185-318), and with w_dev FPDivConstNode
+ * (fpdiv/fpdiv_const.rs:61-99; div_with_const_fixed, honeybadger/mod.rs:1071-1137): a local product with a PUBLIC multiplier per
+ * element, then the same TruncPr.  With v = a * w[i] when w_dev is given and v = a otherwise:
+ *   r'      = sum_{j<m} 2^j r_bits[j]                                   (truncpr.rs:277-283)
+ *   open_sh = (v + 2^(k-1)) + (2^m r_int + r')                          (truncpr.rs:275-297)
+ *   c_open  = open_sh opened: the P(0) decode of degree t that hbmpc_dev_batch_recover_p0 makes of the sender rows -- row s of
+ *             the [party][N] arrays is read as the share of sender_ids[s] (the pipelines pass 0 .. S - 1)
+ *   d       = (v - ((c_open mod 2^m) - r')) 2^-m                        (truncpr.rs:215-220)
+ * a, r_int, r_dash_out, open_sh_out, d_out and c_out (= a * w, required iff w_dev) are [party][N], r_bits [party][m][N], w_dev and
+ * c_open_out [N]; status_out [N] and summary_dev (either may be null) are exactly as hbmpc_dev_batch_recover_p0 leaves them.  A
+ * chunk that fails its verification opens to zero and is counted, and the last step runs on that zero.  Validation is that of
+ * hbmpc_dev_fpmul_parties (k >= 1, m <= 4096, m % 8 == 0 or m < 256, null buffers, N, n, the senders), all of it before the first
+ * launch; w_dev without c_out is InvalidInput.  Fr only.
+ * With exactly 2t + 1 senders and at most hbmpc_set_fused_truncpr elements the call is ONE launch, a wave per element
+ * (csrc/kernels_truncpr_wave.hpp: U29, n <= 64, t <= 30, the element's operands within a workgroup's LDS); otherwise three:
+ * k_truncpr_front (csrc/kernels_elem.hpp), hbmpc_dev_batch_recover_p0, hbmpc_dev_truncpr_finalize_parties.  Every output buffer,
+ * status byte and summary holds the same bytes in both forms. */
+ShareErrorCode hbmpc_dev_truncpr_parties(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const U256* a, const U256* w_dev,
+                                         const U256* r_bits, const U256* r_int, size_t k, size_t m, size_t N, size_t n, size_t t,
+                                         U256* c_out, U256* r_dash_out, U256* open_sh_out, U256* c_open_out, U256* d_out,
+                                         uint8_t* status_out, hbmpc_recover_summary* summary_dev, void* stream);
+/* fpdiv/mod.rs:8-60 fixed_point_reciprocal_scaled, bit for bit, for N denominators (host arithmetic: no context, no device):
+ * b = the LOW 128 bits of the canonical value (its two low limbs: the reference reads 16 bytes), w = (2^(2f) + (b >> 1)) / b in
+ * u128, as an Fr element.  InvalidInput: a null buffer; 2f >= 128 (the reference's shift overflows); a denominator that is zero or
+ * whose low 128 bits are zero (FPDivConstError::InvalidDivisor) -- *first_bad_out (may be null) gets its index, else SIZE_MAX.
+ * Nothing is written to w_out on error. */
+ShareErrorCode hbmpc_fixed_point_reciprocal_scaled(const U256* denom, size_t N, size_t f, U256* w_out, size_t* first_bad_out);
 ShareErrorCode hbmpc_dev_beaver_open_shares_paired(hbmpc_ctx* ctx, const U256* a, const U256* b, const U256* x, const U256* y,
                                                    size_t N, size_t parties, U256* de_sh_out, void* stream);
 ShareErrorCode hbmpc_dev_truncpr_rdash(hbmpc_ctx* ctx, const U256* r_bits, size_t m, size_t N, U256* r_dash_out,
@@ -924,6 +959,9 @@ ShareErrorCode hbmpc_set_producer_fusion(hbmpc_ctx* ctx, int on);
 /* hbmpc_dev_fpmul_parties runs as one launch up to max_elements batch elements (default 2048; 0: always the five separate
  * launches).  Same bytes either way (A/B aid). */
 ShareErrorCode hbmpc_set_fused_fpmul(hbmpc_ctx* ctx, size_t max_elements);
+/* hbmpc_dev_truncpr_parties runs as one launch up to max_elements batch elements (default 768; 0: always the three separate
+ * launches).  Same bytes either way (A/B aid). */
+ShareErrorCode hbmpc_set_fused_truncpr(hbmpc_ctx* ctx, size_t max_elements);
 /* hbmpc_dev_triplegen_parties runs as one launch up to max_chunks chunks of 2t + 1 triples (default 1024; 0: always the four
  * separate launches).  Same bytes either way (A/B aid). */
 ShareErrorCode hbmpc_set_fused_triplegen(hbmpc_ctx* ctx, size_t max_chunks);

@@ -8,6 +8,8 @@
 //                  triple_gen/triple_generation.rs:304-364,164-232; batch_recon/batch_recon.rs:144-185,332-481
 //   FpMul          FPMulNode::init = Multiply (Beaver, RBC path) + TruncPrNode
 //                  fpmul/fpmul.rs:61-110, mul/multiplication.rs:417-426,57-139, fpmul/truncpr.rs:185-318
+//   TruncPr        TruncPrNode on its own                                           fpmul/truncpr.rs:185-318
+//   FpDivConst     FPDivConstNode: a * w for a public reciprocal w, then TruncPr    fpdiv/fpdiv_const.rs:61-99, fpdiv/mod.rs:8-60
 //   RanSha         RanShaNode: deal, n x n Vandermonde, verifier reconstruction + degree test, output slice
 //                  share_gen/share_gen.rs:232-289,401-454,516-530,199-203
 //   RanDouSha      DouShaNode deal + RanDouShaNode: both Vandermonde products, verifier interpolations + tests, output slice
@@ -17,6 +19,7 @@
 // run() only ENQUEUES on the stream; capture() records the same call sequence into a HIP graph after two eager runs and
 // replay() launches it -- at the batch sizes the protocols really use that removes the launch overhead that dominates.
 #pragma once
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -107,6 +110,55 @@ class FpMul : public Pipeline {
         pl_check(hbmpc_pipe_fpmul_create(ctx, n, t, N, k, m, open_senders, stream, &h), ctx, "hbmpc_pipe_fpmul_create");
         return h;
     }
+};
+
+// TruncPr (fpmul/truncpr.rs:185-318) of N values for n parties: k-bit values, m fractional bits dropped.  The caller uploads rbits
+// and rint (what PRandBit / PRandInt produce).  open_senders as in FpMul.
+class TruncPr : public Pipeline {
+  public:
+    TruncPr(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t k, size_t m, void* stream, size_t open_senders = 0)
+        : TruncPr(ctx, n, t, N, k, m, stream, open_senders, 0) {}
+    U256 *a, *rint, *rbits, *rdash, *osh, *cop, *out;  // [party][N] (rbits: [party][bit][N]; cop: [N], the opened value)
+
+  protected:
+    TruncPr(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t k, size_t m, void* stream, size_t open_senders, int with_multiplier)
+        : Pipeline(ctx, create(ctx, n, t, N, k, m, open_senders, with_multiplier, stream), stream) {
+        a = buffer("a"), rint = buffer("rint"), rbits = buffer("rbits"), rdash = buffer("rdash"), osh = buffer("osh"), cop = buffer("cop");
+        out = buffer("out");
+    }
+
+  private:
+    static hbmpc_pipe* create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t k, size_t m, size_t open_senders, int with_multiplier, void* stream) {
+        hbmpc_pipe* h = nullptr;
+        pl_check(hbmpc_pipe_truncpr_create(ctx, n, t, N, k, m, open_senders, with_multiplier, stream, &h), ctx, "hbmpc_pipe_truncpr_create");
+        return h;
+    }
+};
+
+// FPDivConstNode (fpdiv/fpdiv_const.rs:61-99) for n parties: N fixed-point values of k bits with f fractional bits, each divided by a
+// PUBLIC denominator: c = a * w with w = fixed_point_reciprocal_scaled(denominator) (fpdiv/mod.rs:8-60), then TruncPr of c with 2 k
+// bits and m = f.
+class FpDivConst : public TruncPr {
+  public:
+    FpDivConst(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t k, size_t f, void* stream, size_t open_senders = 0)
+        : TruncPr(ctx, n, t, N, 2 * k, f, stream, open_senders, 1), f_(f) {
+        w = buffer("w"), c = buffer("c");
+    }
+    // denom[count], count <= N: the ClearFixedPoint integers; runs the host helper (throws on an invalid divisor), then uploads w
+    void set_denominators(const U256* denom, size_t count) {
+        std::vector<U256> host(count);
+        size_t bad = SIZE_MAX;
+        const ShareErrorCode rc = hbmpc_fixed_point_reciprocal_scaled(denom, count, f_, host.data(), &bad);
+        if (rc != ShareSuccess && bad != SIZE_MAX)
+            throw std::runtime_error("hbmpc_fixed_point_reciprocal_scaled -> " + std::to_string((int)rc) + ": invalid divisor at index " + std::to_string(bad));
+        pl_check(rc, ctx_, "hbmpc_fixed_point_reciprocal_scaled");
+        upload("w", host.data(), count);
+        sync();  // the copy reads `host`
+    }
+    U256 *w, *c;  // [N] the public multipliers; [party][N] = a * w
+
+  private:
+    size_t f_;
 };
 
 class Producer : public Pipeline {

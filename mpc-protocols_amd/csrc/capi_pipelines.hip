@@ -13,6 +13,8 @@
 //                  double_share/double_share_generation.rs:151-215, ran_dou_sha/mod.rs:371-449,569-602,314-331
 //   preprocessing  run_preprocessing's triple part (honeybadger/mod.rs:1239-1393): ransha -> a, b; randousha -> r; triplegen
 //   randbit        RandBit: Beaver square of a, BatchRecon of a^2, phase 2   fpmul/rand_bit.rs:242-293,197-220
+//   truncpr        TruncPrNode alone, or FPDivConstNode = a local product with a public reciprocal + TruncPrNode
+//                  fpmul/truncpr.rs:185-318, fpdiv/fpdiv_const.rs:61-99
 //
 // Host-side orchestration only: this file is a CLIENT of the hbmpc_dev_* entry points (it includes nothing but the public
 // header); every arithmetic step is a device call, buffers never leave HBM, the parties' all-to-all is a layout.
@@ -225,6 +227,37 @@ struct FpMul : hbmpc_pipe {
         PL(hbmpc_dev_fpmul_parties(ctx, ids.data(), ids.size(), ta, tb, tc, x, y, rbits, rint, k, m, N, n, t, desh, dop, z, rdash, osh, cop, out,
                                    status, summ_first, summ, stream));
         check_summary(summ_first);
+        check_summary(summ);
+    }
+};
+
+// TruncPr of N values for n parties (fpmul/truncpr.rs:185-318) and, with a multiplier, FPDivConstNode (fpdiv/fpdiv_const.rs:61-99:
+// c = a * w with the public reciprocal w of the element's denominator, then TruncPr of c with k = 2 k_fixed, m = f).  The
+// caller uploads rbits and rint (PRandBit / PRandInt produce them) and, with a multiplier, w.  open_senders as in FpMul.  Fr only.
+struct TruncPr : hbmpc_pipe {
+    size_t n, t, N, k, m;
+    U256 *a, *rint, *rbits, *rdash, *osh, *out, *c = nullptr, *w = nullptr, *cop;
+    uint8_t* status;
+    std::vector<size_t> ids;
+    TruncPr(hbmpc_ctx* cx, size_t n_, size_t t_, size_t N_, size_t k_, size_t m_, size_t open_senders, int with_multiplier, void* s)
+        : hbmpc_pipe(cx, s), n(n_), t(t_), N(N_), k(k_), m(m_) {
+        if (f.gl) throw PipeError{TypeMismatch};
+        if (open_senders == 0) open_senders = 2 * t + 1;
+        if (n == 0 || N == 0 || open_senders < 2 * t + 1 || open_senders > n) throw PipeError{InvalidInput};
+        arena(((6 + m) * n * N + 2 * N) * 32 + N + (1 << 14));
+        a = reinterpret_cast<U256*>(take("a", n * N)), rint = reinterpret_cast<U256*>(take("rint", n * N));
+        rbits = reinterpret_cast<U256*>(take("rbits", n * m * N));  // [party][bit][N]
+        rdash = reinterpret_cast<U256*>(take("rdash", n * N)), osh = reinterpret_cast<U256*>(take("osh", n * N));
+        out = reinterpret_cast<U256*>(take("out", n * N));
+        if (with_multiplier) c = reinterpret_cast<U256*>(take("c", n * N)), w = reinterpret_cast<U256*>(take("w", N));
+        cop = reinterpret_cast<U256*>(take("cop", N));
+        status = take_bytes("status", N, N);
+        summ = reinterpret_cast<hbmpc_recover_summary*>(take_bytes("summary", 64, 16));
+        for (size_t i = 0; i < open_senders; ++i) ids.push_back(i);
+    }
+    void run() override {
+        // one launch for a small batch, three otherwise (hbmpc_dev_truncpr_parties); checked mode looks at the open's summary afterwards
+        PL(hbmpc_dev_truncpr_parties(ctx, ids.data(), ids.size(), a, w, rbits, rint, k, m, N, n, t, c, rdash, osh, cop, out, status, summ, stream));
         check_summary(summ);
     }
 };
@@ -588,6 +621,10 @@ extern "C" ShareErrorCode hbmpc_pipe_triplegen_create(hbmpc_ctx* ctx, size_t n, 
 extern "C" ShareErrorCode hbmpc_pipe_fpmul_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t k, size_t m, size_t open_senders,
                                                   void* stream, hbmpc_pipe** pipe_out) {
     return create<FpMul>(ctx, pipe_out, n, t, N, k, m, open_senders, stream);
+}
+extern "C" ShareErrorCode hbmpc_pipe_truncpr_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t k, size_t m, size_t open_senders,
+                                                    int with_multiplier, void* stream, hbmpc_pipe** pipe_out) {
+    return create<TruncPr>(ctx, pipe_out, n, t, N, k, m, open_senders, with_multiplier, stream);
 }
 extern "C" ShareErrorCode hbmpc_pipe_ransha_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t K, size_t verify_senders, void* stream,
                                                    hbmpc_pipe** pipe_out) {

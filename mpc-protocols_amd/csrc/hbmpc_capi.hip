@@ -19,6 +19,7 @@
 #include "fr_gold.hpp"
 #include "elem_args.hpp"
 #include "kernels_fpmul_wave.hpp"
+#include "kernels_truncpr_wave.hpp"
 #include "kernels_triplegen_wg.hpp"
 #include "launchers.hpp"
 #include "tables.hpp"
@@ -70,6 +71,7 @@ struct hbmpc_ctx {
     size_t pair_decode_min = 8192;                // hbmpc_dev_fpmul_parties: from this many elements the first open forms its shares at load time
     size_t fused_triplegen_max = 1024;             // hbmpc_dev_triplegen_parties: one launch (a workgroup per chunk of 2t + 1 triples) up to this many chunks (0: never)
     size_t fused_fpmul_max = 2048;                 // hbmpc_dev_fpmul_parties: one launch (a wave per element) up to this many elements (0: never)
+    size_t fused_truncpr_max = 768;                // hbmpc_dev_truncpr_parties: the same (profiles/fused_truncpr_sweep.txt: ahead or level, eager and replayed)
     bool gather_row_copies = false;                // hbmpc_dev_gather_party_major: take the per-row peer copies even where the 2-D copy applies (A/B aid)
     bool list_rows_in_kernel = true;               // the producers' mixing step writes the parties' lists itself (k_mfma_bfly<.., LISTS>)
     bool mfma_bfly = true;                         // large encodes take the domain points in pairs (kernels_mfma_bfly.hpp)
@@ -405,6 +407,11 @@ extern "C" ShareErrorCode hbmpc_set_matrix_cores(hbmpc_ctx* ctx, int on, size_t 
 extern "C" ShareErrorCode hbmpc_set_fused_fpmul(hbmpc_ctx* ctx, size_t max_elements) {
     if (!ctx) return InvalidInput;
     ctx->fused_fpmul_max = max_elements;
+    return ShareSuccess;
+}
+extern "C" ShareErrorCode hbmpc_set_fused_truncpr(hbmpc_ctx* ctx, size_t max_elements) {
+    if (!ctx) return InvalidInput;
+    ctx->fused_truncpr_max = max_elements;
     return ShareSuccess;
 }
 extern "C" ShareErrorCode hbmpc_set_fused_triplegen(hbmpc_ctx* ctx, size_t max_chunks) {
@@ -2241,3 +2248,5 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
     if (rc != ShareSuccess) return rc;
     return hbmpc_dev_truncpr_finalize_parties(ctx, z_out, r_dash_out, c_open_out, m, N, n, d_out, stream);
 }
+
+#include "capi_truncpr.inc"

@@ -275,6 +275,50 @@ __global__ __launch_bounds__(256) void k_fpmul_middle(const uint32_t* __restrict
         F::store_loose(open_out + ip * F::EW, o);
     }
 }
+// TruncPrNode before its open, for every party in ONE launch; with HAS_W the local product of FPDivConstNode in front of it
+// (fpdiv/fpdiv_const.rs:79, truncpr.rs:275-297) --
+//   c = a w (HAS_W; v = c, else v = a);   r' = sum_j 2^j r_bits[j];   open = (v + 2^(k-1)) + (2^m r_int + r')
+// w public [N] canonical; everything else [party][N] (r_bits [party][m][N]): one pass over a party's m + 2 inputs.  cs as
+// k_fpmul_middle's.  The loop serves any gridDim.y, with w's Montgomery form made once per thread; the host launches a grid row
+// per party at every size (one trip, w converted per party: capi_truncpr.inc has the measurement that decided it).
+template <class F, bool HAS_W>
+__global__ __launch_bounds__(256) void k_truncpr_front(const uint32_t* __restrict__ a, const uint32_t* __restrict__ w,
+                                                       const uint32_t* __restrict__ r_bits, const uint32_t* __restrict__ r_int,
+                                                       int m, size_t N, ElemConsts cs, const uint32_t* __restrict__ pow2,
+                                                       uint32_t* __restrict__ c, uint32_t* __restrict__ r_dash,
+                                                       uint32_t* __restrict__ open_out, unsigned parties) {
+    using E = typename F::E;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    E wm;
+    if constexpr (HAS_W) wm = F::mulc(F::load(w + i * F::EW), cs.r2);
+    for (unsigned p = blockIdx.y; p < parties; p += gridDim.y) {
+        const size_t ip = (size_t)p * N + i;
+        E v = F::load(a + ip * F::EW);
+        if constexpr (HAS_W) {
+            v = F::canon_loose(F::mont(v, wm));  // the canonical c: what the open and the last step would load
+            F::store_lt2r(c + ip * F::EW, v);
+        }
+        typename F::Acc ra;
+        F::acc_zero(ra);
+        int pending = 0;
+        for (int j = 0; j < m; ++j) {
+            if (pending == F::MAX_DOT_TERMS) {
+                F::acc_fold(ra);
+                pending = 1;
+            }
+            F::acc_mac(ra, F::load(r_bits + (((size_t)p * m + j) * N + i) * F::EW), pow2 + (size_t)j * F::NL);
+            ++pending;
+        }
+        F::acc_fold(ra);
+        const E rd = F::canon_loose(F::acc_reduce(ra));
+        F::store_lt2r(r_dash + ip * F::EW, rd);
+        E o = F::add(v, F::load_const(cs.c1));
+        o = F::add(o, F::mulc(F::load(r_int + ip * F::EW), cs.c0));
+        o = F::add(o, rd);
+        F::store_loose(open_out + ip * F::EW, o);
+    }
+}
 // truncpr.rs:215-220 + fpmul/mod.rs:381-406:  d = (a - ((c mod 2^m) - r_dash)) * (2^m)^-1;  cs.c0 = (2^m)^-1
 template <class F>
 __global__ __launch_bounds__(256) void k_truncpr_finalize(const uint32_t* __restrict__ a,

@@ -116,6 +116,9 @@ struct FpmulWaveArgs;
 struct TripleGenWgArgs;
 void launch_triplegen_wg(int impl, const TripleGenWgArgs& a, hipStream_t s);  // TripleGenNode, a workgroup per chunk (kernels_triplegen_wg.hpp): U29 or Goldilocks
 bool launch_fpmul_wave(const FpmulWaveArgs& a, int device, hipStream_t s, bool dry_run);
+// TruncPrNode / FPDivConstNode (a.w set) the same way (kernels_truncpr_wave.hpp); dry_run: only say whether the LDS layout fits
+struct TruncprWaveArgs;
+bool launch_truncpr_wave(const TruncprWaveArgs& a, int device, hipStream_t s, bool dry_run);
 // flagged chunks: two cheap interpolation candidates before the OEC/Gao kernel (k_second_chance)
 void launch_second_chance(int impl, const SecondArgs& a, unsigned grid, hipStream_t s);
 bool launch_second_chance_m(int m, const SecondArgs& a, unsigned grid, hipStream_t s);  // U29, m = 2 .. 16 at compile time; false otherwise
@@ -180,6 +183,9 @@ void launch_truncpr_open(int impl, const uint32_t* a, const uint32_t* r_dash, co
 void launch_fpmul_middle(int impl, const uint32_t* c, const uint32_t* x, const uint32_t* y, const uint32_t* d, const uint32_t* e, const uint32_t* r_bits,
                          const uint32_t* r_int, int m, size_t N, const ElemConsts& cs, const uint32_t* pow2, uint32_t* z, uint32_t* r_dash,
                          uint32_t* open_out, unsigned parties, unsigned grid_parties, hipStream_t s);
+void launch_truncpr_front(int impl, const uint32_t* a, const uint32_t* w, const uint32_t* r_bits, const uint32_t* r_int, int m, size_t N,
+                          const ElemConsts& cs, const uint32_t* pow2, uint32_t* c, uint32_t* r_dash, uint32_t* open_out, unsigned parties,
+                          unsigned grid_parties, hipStream_t s);  // w null: no multiplier (c is not written)
 void launch_truncpr_finalize(int impl, const uint32_t* a, const uint32_t* r_dash, const uint32_t* c_open, int m, size_t N, unsigned parties,
                              const ElemConsts& cs, uint32_t* d_out, hipStream_t s);
 void launch_modmul_ubench(int impl, uint32_t* out, size_t threads, uint32_t iters, const ElemConsts& cs, hipStream_t s);

@@ -55,6 +55,15 @@ void launch_fpmul_middle(int impl, const uint32_t* c, const uint32_t* x, const u
     by_fr_impl(impl, [&](auto f) { hipLaunchKernelGGL((k_fpmul_middle<field_t<decltype(f)>>), elem_grid(N, grid_parties), dim3(256), 0, s,
                        c, x, y, d, e, r_bits, r_int, m, N, cs, pow2, z, r_dash, open_out, parties); });
 }
+void launch_truncpr_front(int impl, const uint32_t* a, const uint32_t* w, const uint32_t* r_bits, const uint32_t* r_int, int m, size_t N,
+                          const ElemConsts& cs, const uint32_t* pow2, uint32_t* c, uint32_t* r_dash, uint32_t* open_out, unsigned parties,
+                          unsigned grid_parties, hipStream_t s) {
+    by_fr_impl(impl, [&](auto f) {
+        using F = field_t<decltype(f)>;
+        if (w) hipLaunchKernelGGL((k_truncpr_front<F, true>), elem_grid(N, grid_parties), dim3(256), 0, s, a, w, r_bits, r_int, m, N, cs, pow2, c, r_dash, open_out, parties);
+        else hipLaunchKernelGGL((k_truncpr_front<F, false>), elem_grid(N, grid_parties), dim3(256), 0, s, a, w, r_bits, r_int, m, N, cs, pow2, c, r_dash, open_out, parties);
+    });
+}
 void launch_truncpr_finalize(int impl, const uint32_t* a, const uint32_t* r_dash, const uint32_t* c_open, int m, size_t N, unsigned parties,
                              const ElemConsts& cs, uint32_t* d_out, hipStream_t s) {
     by_fr_impl(impl, [&](auto f) { hipLaunchKernelGGL((k_truncpr_finalize<field_t<decltype(f)>>), elem_grid(N, parties), dim3(256), 0, s, a, r_dash, c_open, m, N, cs, d_out); });

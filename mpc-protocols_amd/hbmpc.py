@@ -74,6 +74,19 @@ def riss_tsets(n, t):
     return rc, [tuple(int(x) for x in row) for row in ids]
 
 
+FUSED_TRUNCPR_DEFAULT = 768  # hbmpc_set_fused_truncpr's default (csrc/hbmpc_capi.hip)
+
+
+def fixed_point_reciprocal_scaled(denom, f):
+    """(rc, w, first_bad): hbmpc_fixed_point_reciprocal_scaled -- fpdiv/mod.rs:8-60 for N denominators ([N] U256 -> [N] U256); host
+    only, needs no device.  first_bad: the index of the first invalid divisor, or None"""
+    denom = np.ascontiguousarray(denom, dtype=np.uint64)
+    N = denom.shape[0]
+    w, bad = u256((N,)), C.c_size_t()
+    rc = lib().hbmpc_fixed_point_reciprocal_scaled(_p(denom), C.c_size_t(N), C.c_size_t(f), _p(w), C.byref(bad))
+    return rc, w, (None if bad.value == C.c_size_t(-1).value else bad.value)
+
+
 class Engine:
     """One hbmpc_ctx on one GPU.  Host-pointer calls take/return numpy U256 arrays; the
     dev_* calls take raw device pointers (ints, e.g. torch.Tensor.data_ptr()) and a stream."""
@@ -526,6 +539,21 @@ class Engine:
                                               C.c_size_t(k), C.c_size_t(m), C.c_size_t(N), C.c_size_t(n), C.c_size_t(t),
                                               *(C.c_void_p(p) for p in (de_ws_d, de_d, z_d, rdash_d, osh_d, cop_d, out_d, status_d, summary_first_d, summary_d)),
                                               C.c_void_p(stream))
+
+    def dev_truncpr_parties(self, sender_ids, a_d, w_d, rbits_d, rint_d, k, m, N, n, t, c_d, rdash_d, osh_d, cop_d, out_d, status_d=0,
+                            summary_d=0, stream=0):
+        """TruncPrNode (w_d = 0) or FPDivConstNode (w_d: the public multipliers [N]; c_d then receives a * w) for all n parties of this
+        device in one call (hbmpc_dev_truncpr_parties): one launch for a small batch, three otherwise; returns the ShareErrorCode"""
+        ids = (C.c_size_t * len(sender_ids))(*sender_ids)
+        return self.L.hbmpc_dev_truncpr_parties(self.ctx, ids, C.c_size_t(len(sender_ids)),
+                                                *(C.c_void_p(p) for p in (a_d, w_d, rbits_d, rint_d)),
+                                                C.c_size_t(k), C.c_size_t(m), C.c_size_t(N), C.c_size_t(n), C.c_size_t(t),
+                                                *(C.c_void_p(p) for p in (c_d, rdash_d, osh_d, cop_d, out_d, status_d, summary_d)),
+                                                C.c_void_p(stream))
+
+    def set_fused_truncpr(self, max_elements: int):
+        """hbmpc_dev_truncpr_parties is one launch up to this many batch elements (0: always three)"""
+        assert self.L.hbmpc_set_fused_truncpr(self.ctx, C.c_size_t(max_elements)) == 0
 
     def dev_beaver_open_shares_paired(self, a_d, b_d, x_d, y_d, N, parties, de_d, stream=0):
         """de[party][0][N] = a - x, de[party][1][N] = b - y: one P(0) decode over 2 N values per sender opens both"""

@@ -12,6 +12,8 @@ in the library; this file only names things for the tests and bench.py.
   RanDouSha      DouShaNode::init_batch + RanDouShaNode::init_batch + reconstruction_handler + try_finalize
                  double_share/double_share_generation.rs:151-215, ran_dou_sha/mod.rs:371-449,569-602,314-331
   Preprocessing  run_preprocessing's triple part (honeybadger/mod.rs:1239-1393): RanSha -> a, b; RanDouSha -> r; TripleGen
+  TruncPr        TruncPrNode on its own                                      fpmul/truncpr.rs:185-318
+  FpDivConst     FPDivConstNode: a * w for a public reciprocal w, then TruncPr   fpdiv/fpdiv_const.rs:61-99, fpdiv/mod.rs:8-60
   RandBit        RandBit: Beaver square of a, BatchRecon of a^2, phase 2   fpmul/rand_bit.rs:242-293,197-220
   PRandInt       fold of the RISS contributions, conversion to Fr shares   fpmul/prandbitd.rs:667-684,311-356
   PRandBit       ... and to Goldilocks and GF(2^8), open r + b, finalize   fpmul/prandbitd.rs:311-356,437-446,189-211
@@ -146,6 +148,51 @@ class FpMul(_Pipe):
 
     def download(self, which="out"):
         return self.download_named(which, (self.n, self.N))
+
+
+class TruncPr(_Pipe):
+    """TruncPr (fpmul/truncpr.rs:185-318) of N values for n parties: k-bit values, m fractional bits dropped.  Buffers a, rint, rdash,
+    osh, out are [party][N], rbits [party][m][N], cop [N] the opened value, status [N] bytes, summary the open's.  open_senders as in
+    FpMul.  run() is one library call (hbmpc_dev_truncpr_parties): ONE launch up to hbmpc_set_fused_truncpr elements when the open
+    has exactly 2t + 1 senders, three launches otherwise."""
+    _with_multiplier = 0
+
+    def __init__(self, eng, n, t, N, k, m, stream=0, open_senders=None):
+        self.n, self.t, self.N, self.k, self.m = n, t, N, k, m
+        self.open_senders = 2 * t + 1 if open_senders is None else open_senders
+        h = C.c_void_p()
+        rc = eng.L.hbmpc_pipe_truncpr_create(eng.ctx, *[C.c_size_t(v) for v in (n, t, N, k, m, self.open_senders)], C.c_int(self._with_multiplier),
+                                             C.c_void_p(stream), C.byref(h))
+        if rc != 0:
+            raise RuntimeError(f"hbmpc_pipe_truncpr_create{(n, t, N, k, m, self.open_senders, self._with_multiplier)} -> ShareErrorCode {rc}: {eng.last_error()}")
+        super().__init__(eng, h, stream)
+
+    def upload(self, a, rbits, rint):
+        for name, src in (("a", a), ("rbits", rbits), ("rint", rint)):
+            self.upload_named(name, src)
+
+    def download(self, which="out"):
+        return self.download_named(which, (self.N,) if which in ("cop", "w") else (self.n, self.N))
+
+
+class FpDivConst(TruncPr):
+    """FPDivConstNode (fpdiv/fpdiv_const.rs:61-99) for n parties: N fixed-point values of k bits with f fractional bits, each divided
+    by a PUBLIC denominator -- c = a * w with w = fixed_point_reciprocal_scaled(denominator) (fpdiv/mod.rs:8-60), then TruncPr of c
+    with 2 k bits and m = f.  Adds the buffers w [N] and c [party][N]."""
+    _with_multiplier = 1
+
+    def __init__(self, eng, n, t, N, k, f, stream=0, open_senders=None):
+        self.k_fixed, self.f = k, f
+        super().__init__(eng, n, t, N, 2 * k, f, stream=stream, open_senders=open_senders)
+
+    def set_denominators(self, denom):
+        """denom [N] canonical field elements (the integers of ClearFixedPoint): runs the host helper, uploads w; raises on an invalid divisor"""
+        from .hbmpc import fixed_point_reciprocal_scaled
+        rc, w, bad = fixed_point_reciprocal_scaled(denom, self.f)
+        if rc != 0:
+            raise RuntimeError(f"hbmpc_fixed_point_reciprocal_scaled -> ShareErrorCode {rc} (first invalid divisor: {bad})")
+        self.upload_named("w", w)
+        return w
 
 
 class _Producer(_Pipe):

@@ -313,6 +313,29 @@ impl GpuShares {
         let rc = unsafe { sys::hbmpc_pipe_fpmul_create(self.ctx, n, t, pairs, k, m, 0, stream, &mut p) };
         self.wrap(rc, p, n)
     }
+    /// `TruncPrNode` on its own for all n parties (fpmul/truncpr.rs:185-318): buffers a, rint ([party][values]), rbits ([party][m][values])
+    pub fn pipe_truncpr(&self, n: usize, t: usize, values: usize, k: usize, m: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_truncpr_create(self.ctx, n, t, values, k, m, 0, 0, stream, &mut p) };
+        self.wrap(rc, p, n)
+    }
+    /// `FPDivConstNode::init` for all n parties (fpdiv/fpdiv_const.rs:61-99): values of `k` bits with `f` fractional bits, each divided by
+    /// its public denominator (the integers of `ClearFixedPoint`).  The reciprocals are `fixed_point_reciprocal_scaled`'s
+    /// (fpdiv/mod.rs:8-60) and are uploaded as `w`; an invalid divisor is `InvalidInput`, as `FPDivConstError::InvalidDivisor` there
+    pub fn pipe_fpdiv_const(&self, n: usize, t: usize, k: usize, f: usize, denominators: &[Fr], stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
+        let d: Vec<sys::U256> = denominators.iter().map(to_u256).collect();
+        let mut w = vec![sys::U256::default(); d.len()];
+        let rc = unsafe { sys::hbmpc_fixed_point_reciprocal_scaled(d.as_ptr(), d.len(), f, w.as_mut_ptr(), std::ptr::null_mut()) };
+        self.check(rc, n)?;
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_truncpr_create(self.ctx, n, t, d.len(), 2 * k, f, 0, 1, stream, &mut p) };
+        let pipe = self.wrap(rc, p, n)?;
+        let rc = unsafe { sys::hbmpc_pipe_upload(pipe.pipe, GpuPipeline::name("w").as_ptr(), w.as_ptr() as *const core::ffi::c_void, w.len()) };
+        self.check(rc, n)?;
+        let rc = unsafe { sys::hbmpc_pipe_sync(pipe.pipe) };  // the copy reads `w`
+        self.check(rc, n)?;
+        Ok(pipe)
+    }
     /// `RanShaNode` for all n parties, `batch` elements per dealer (share_gen/share_gen.rs:232-289,401-454,516-530)
     pub fn pipe_ransha(&self, n: usize, t: usize, batch: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
         let mut p = std::ptr::null_mut();
