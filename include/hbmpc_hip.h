@@ -200,6 +200,7 @@ void hbmpc_graph_destroy(hbmpc_graph* graph);
  *   triplegen      a, b, r2t, rt (inputs [n][N]); c (output [n][N]); Y, Z, opened, status, summary
  *   fpmul          x, y, ta, tb, tc, rint ([n][N]), rbits ([n][m][N]) (inputs); out ([n][N]); z, rdash, osh, desh, dop, eop, cop
  *   truncpr        a, rint, rbits (inputs; w with a multiplier); out; c, rdash, osh, cop, status, summary (see its create call)
+ *   mul            x, y, ta, tb, tc (inputs [n][N]); out ([n][N] = z); desh ([n][2][N]); deop ([2 N]; dop, eop its halves); status (2 N bytes); summary
  *   ransha         coeffs ([dealer][K][t+1], column 0 the secret); S ([dealer][recipient][K]); y; out ([party][K][n-2t]); bad
  *   randousha      coeffs_t, coeffs_2t; S_t, S_2t; y_t, y_2t; out_t, out_2t ([party][K][t+1]); bad
  *   preprocessing  its parts by name (hbmpc_pipe_part: "ransha", "randousha", "triplegen"; borrowed handles)
@@ -220,6 +221,11 @@ ShareErrorCode hbmpc_pipe_fpmul_create(hbmpc_ctx* ctx, size_t n, size_t t, size_
  * ([n][N]); rdash, osh ([n][N]); cop ([N]); status ([N] bytes); summary.  TypeMismatch on a Goldilocks context. */
 ShareErrorCode hbmpc_pipe_truncpr_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t k, size_t m, size_t open_senders,
                                          int with_multiplier, void* stream, hbmpc_pipe** pipe_out);
+/* Multiply (Beaver; honeybadger/mod.rs:543-628, mul/multiplication.rs:417-426,102-139,57-100) of N element pairs for n parties, over
+ * either field: out = the parties' shares of x * y from one triple (ta, tb, tc) per pair.  run() is hbmpc_dev_mul_parties /
+ * hbmpc_gl_dev_mul_parties.  Buffers: x, y, ta, tb, tc (inputs [n][N]); out ([n][N]); desh ([n][2][N]); deop ([2 N]: the opened
+ * ta - x, then the opened tb - y; dop and eop name its halves); status (2 N bytes); summary.  open_senders as in fpmul. */
+ShareErrorCode hbmpc_pipe_mul_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t open_senders, void* stream, hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_ransha_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t K, size_t verify_senders, void* stream,
                                         hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_randousha_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t K, void* stream, hbmpc_pipe** pipe_out);
@@ -566,6 +572,28 @@ ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* sender_ids,
                                        size_t n, size_t t, U256* de_sh_ws, U256* de_out, U256* z_out, U256* r_dash_out, U256* open_sh_out,
                                        U256* c_open_out, U256* d_out, uint8_t* status_out, hbmpc_recover_summary* summary_first_dev,
                                        hbmpc_recover_summary* summary_dev, void* stream);
+/* Multiply (Beaver) for every party of this device in one call (honeybadger/mod.rs:543-628; mul_int, :1177-1223, wraps it): the
+ * shares it opens (mul/multiplication.rs:417-426), the open (:102-139) and finalize_mul (:57-100):
+ *   de_out  = a - x, then b - y, opened: the P(0) decode of degree t over the 2 N values of a sender row
+ *   z       = c - (e + y) d - x e
+ * a, b, c (the triple), x, y and z_out are [party][N]; de_out is [2 N]; sender_ids[S] are PARTY ids, as in hbmpc_dev_fpmul_parties.
+ * status_out[2 N] and summary_dev (either may be null) hold exactly what hbmpc_dev_batch_recover_p0 leaves for G = 2 N from the
+ * senders' rows of the [party][2][N] shares: chunk g is the a - x of element g, chunk N + g its b - y.  A chunk that fails its
+ * verification opens to zero and is counted, and finalize_mul runs on that zero.  All validation (null buffers, N == 0, n == 0,
+ * n > 255, the senders) happens before the first launch: a call that is refused has written nothing.
+ * With exactly 2t + 1 senders and at most hbmpc_set_fused_mul elements (default 1024) the Fr call is ONE launch, a wave per element
+ * (csrc/kernels_mul_wave.hpp: U29, n <= 64, t <= 30); otherwise three: hbmpc_dev_beaver_open_shares_paired, the P(0) decode with
+ * every sender's row read in place (hbmpc_dev_batch_recover_slots), hbmpc_dev_beaver_finalize_parties -- the first two as one from
+ * hbmpc_set_fpmul_pair_decode elements on.  The Goldilocks call is always the three hbmpc_gl_* launches.  Every output buffer,
+ * status byte and summary holds the same bytes in every form; de_sh_ws [party][2][N] is the workspace of the three-launch form
+ * (contents unspecified afterwards).  TypeMismatch: the Fr call on a Goldilocks context and the other way round. */
+ShareErrorCode hbmpc_dev_mul_parties(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const U256* a, const U256* b, const U256* c,
+                                     const U256* x, const U256* y, size_t N, size_t n, size_t t, U256* de_sh_ws, U256* de_out, U256* z_out,
+                                     uint8_t* status_out, hbmpc_recover_summary* summary_dev, void* stream);
+ShareErrorCode hbmpc_gl_dev_mul_parties(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const uint64_t* a, const uint64_t* b,
+                                        const uint64_t* c, const uint64_t* x, const uint64_t* y, size_t N, size_t n, size_t t,
+                                        uint64_t* de_sh_ws, uint64_t* de_out, uint64_t* z_out, uint8_t* status_out,
+                                        hbmpc_recover_summary* summary_dev, void* stream);
 /* TruncPrNode on its own for every party of this device (fpmul/truncpr.rs:185-318), and with w_dev FPDivConstNode
  * (fpdiv/fpdiv_const.rs:61-99; div_with_const_fixed, honeybadger/mod.rs:1071-1137): a local product with a PUBLIC multiplier per
  * element, then the same TruncPr.  With v = a * w[i] when w_dev is given and v = a otherwise:
@@ -962,6 +990,9 @@ ShareErrorCode hbmpc_set_fused_fpmul(hbmpc_ctx* ctx, size_t max_elements);
 /* hbmpc_dev_truncpr_parties runs as one launch up to max_elements batch elements (default 768; 0: always the three separate
  * launches).  Same bytes either way (A/B aid). */
 ShareErrorCode hbmpc_set_fused_truncpr(hbmpc_ctx* ctx, size_t max_elements);
+/* hbmpc_dev_mul_parties runs as one launch up to max_elements batch elements (default 1024; 0: always the three separate
+ * launches).  Same bytes either way (A/B aid). */
+ShareErrorCode hbmpc_set_fused_mul(hbmpc_ctx* ctx, size_t max_elements);
 /* hbmpc_dev_triplegen_parties runs as one launch up to max_chunks chunks of 2t + 1 triples (default 1024; 0: always the four
  * separate launches).  Same bytes either way (A/B aid). */
 ShareErrorCode hbmpc_set_fused_triplegen(hbmpc_ctx* ctx, size_t max_chunks);

@@ -8,6 +8,8 @@
 //                  triple_gen/triple_generation.rs:304-364,164-232; batch_recon/batch_recon.rs:144-185,332-481
 //   FpMul          FPMulNode::init = Multiply (Beaver, RBC path) + TruncPrNode
 //                  fpmul/fpmul.rs:61-110, mul/multiplication.rs:417-426,57-139, fpmul/truncpr.rs:185-318
+//   Mul            Multiply (Beaver, RBC path): the opened shares, the open, finalize_mul
+//                  honeybadger/mod.rs:543-628, mul/multiplication.rs:417-426,102-139,57-100
 //   TruncPr        TruncPrNode on its own                                           fpmul/truncpr.rs:185-318
 //   FpDivConst     FPDivConstNode: a * w for a public reciprocal w, then TruncPr    fpdiv/fpdiv_const.rs:61-99, fpdiv/mod.rs:8-60
 //   RanSha         RanShaNode: deal, n x n Vandermonde, verifier reconstruction + degree test, output slice
@@ -108,6 +110,27 @@ class FpMul : public Pipeline {
     static hbmpc_pipe* create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t k, size_t m, size_t open_senders, void* stream) {
         hbmpc_pipe* h = nullptr;
         pl_check(hbmpc_pipe_fpmul_create(ctx, n, t, N, k, m, open_senders, stream, &h), ctx, "hbmpc_pipe_fpmul_create");
+        return h;
+    }
+};
+
+// Multiply (Beaver; honeybadger/mod.rs:543-628) of N element pairs for n parties over Fr: out = the parties' shares of x * y from one
+// triple (ta, tb, tc) per pair.  open_senders as in FpMul.  (A Goldilocks context takes the same handle through the C ABI; this
+// class names its buffers as U256.)
+class Mul : public Pipeline {
+  public:
+    Mul(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream, size_t open_senders = 0)
+        : Pipeline(ctx, create(ctx, n, t, N, open_senders, stream), stream) {
+        x = buffer("x"), y = buffer("y"), ta = buffer("ta"), tb = buffer("tb"), tc = buffer("tc"), out = buffer("out");
+        desh = buffer("desh"), deop = buffer("deop"), dop = buffer("dop"), eop = buffer("eop");
+    }
+    U256 *x, *y, *ta, *tb, *tc, *out;  // [party][N]
+    U256 *desh, *deop, *dop, *eop;     // [party][2][N]; [2 N] the opened ta - x then tb - y; dop, eop: its halves
+
+  private:
+    static hbmpc_pipe* create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t open_senders, void* stream) {
+        hbmpc_pipe* h = nullptr;
+        pl_check(hbmpc_pipe_mul_create(ctx, n, t, N, open_senders, stream, &h), ctx, "hbmpc_pipe_mul_create");
         return h;
     }
 };

@@ -15,6 +15,8 @@
 //   randbit        RandBit: Beaver square of a, BatchRecon of a^2, phase 2   fpmul/rand_bit.rs:242-293,197-220
 //   truncpr        TruncPrNode alone, or FPDivConstNode = a local product with a public reciprocal + TruncPrNode
 //                  fpmul/truncpr.rs:185-318, fpdiv/fpdiv_const.rs:61-99
+//   mul            Multiply (Beaver, RBC path): the opened shares, the open, finalize_mul
+//                  honeybadger/mod.rs:543-628, mul/multiplication.rs:417-426,102-139,57-100
 //
 // Host-side orchestration only: this file is a CLIENT of the hbmpc_dev_* entry points (it includes nothing but the public
 // header); every arithmetic step is a device call, buffers never leave HBM, the parties' all-to-all is a layout.
@@ -258,6 +260,38 @@ struct TruncPr : hbmpc_pipe {
     void run() override {
         // one launch for a small batch, three otherwise (hbmpc_dev_truncpr_parties); checked mode looks at the open's summary afterwards
         PL(hbmpc_dev_truncpr_parties(ctx, ids.data(), ids.size(), a, w, rbits, rint, k, m, N, n, t, c, rdash, osh, cop, out, status, summ, stream));
+        check_summary(summ);
+    }
+};
+
+// Multiply (Beaver) of N element pairs for n parties (honeybadger/mod.rs:543-628, mul/multiplication.rs:417-426,102-139,57-100):
+// a - x and b - y opened by direct robust interpolation, then finalize_mul.  open_senders as in FpMul.  Either field.
+struct Mul : hbmpc_pipe {
+    size_t n, t, N;
+    unsigned char *x, *y, *ta, *tb, *tc, *out, *desh, *deop;
+    uint8_t* status;
+    std::vector<size_t> ids;
+    Mul(hbmpc_ctx* cx, size_t n_, size_t t_, size_t N_, size_t open_senders, void* s) : hbmpc_pipe(cx, s), n(n_), t(t_), N(N_) {
+        if (open_senders == 0) open_senders = 2 * t + 1;
+        if (n == 0 || N == 0 || open_senders < 2 * t + 1 || open_senders > n) throw PipeError{InvalidInput};
+        arena((8 * n * N + 2 * N) * f.eb + 2 * N + (1 << 14));
+        x = take("x", n * N), y = take("y", n * N), ta = take("ta", n * N), tb = take("tb", n * N), tc = take("tc", n * N);
+        out = take("out", n * N);
+        desh = take("desh", 2 * n * N);  // [party][2][N]: a party's shares of a - x and of b - y side by side
+        deop = take("deop", 2 * N);      // the opened a - x [N], then the opened b - y [N]
+        buffers["dop"] = Buffer{deop, N}, buffers["eop"] = Buffer{deop + N * f.eb, N};
+        status = take_bytes("status", 2 * N, 2 * N);
+        summ = reinterpret_cast<hbmpc_recover_summary*>(take_bytes("summary", 64, 16));
+        for (size_t i = 0; i < open_senders; ++i) ids.push_back(i);
+    }
+    void run() override {
+        // one launch for a small batch over Fr, three otherwise (hbmpc_[gl_]dev_mul_parties); checked mode looks at the open's summary afterwards
+        if (f.gl)
+            PL(hbmpc_gl_dev_mul_parties(ctx, ids.data(), ids.size(), (const uint64_t*)ta, (const uint64_t*)tb, (const uint64_t*)tc, (const uint64_t*)x,
+                                        (const uint64_t*)y, N, n, t, (uint64_t*)desh, (uint64_t*)deop, (uint64_t*)out, status, summ, stream));
+        else
+            PL(hbmpc_dev_mul_parties(ctx, ids.data(), ids.size(), (const U256*)ta, (const U256*)tb, (const U256*)tc, (const U256*)x, (const U256*)y, N, n,
+                                     t, (U256*)desh, (U256*)deop, (U256*)out, status, summ, stream));
         check_summary(summ);
     }
 };
@@ -625,6 +659,10 @@ extern "C" ShareErrorCode hbmpc_pipe_fpmul_create(hbmpc_ctx* ctx, size_t n, size
 extern "C" ShareErrorCode hbmpc_pipe_truncpr_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t k, size_t m, size_t open_senders,
                                                     int with_multiplier, void* stream, hbmpc_pipe** pipe_out) {
     return create<TruncPr>(ctx, pipe_out, n, t, N, k, m, open_senders, with_multiplier, stream);
+}
+extern "C" ShareErrorCode hbmpc_pipe_mul_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t open_senders, void* stream,
+                                                hbmpc_pipe** pipe_out) {
+    return create<Mul>(ctx, pipe_out, n, t, N, open_senders, stream);
 }
 extern "C" ShareErrorCode hbmpc_pipe_ransha_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t K, size_t verify_senders, void* stream,
                                                    hbmpc_pipe** pipe_out) {

@@ -20,6 +20,7 @@
 #include "elem_args.hpp"
 #include "kernels_fpmul_wave.hpp"
 #include "kernels_truncpr_wave.hpp"
+#include "kernels_mul_wave.hpp"
 #include "kernels_triplegen_wg.hpp"
 #include "launchers.hpp"
 #include "tables.hpp"
@@ -72,6 +73,7 @@ struct hbmpc_ctx {
     size_t fused_triplegen_max = 1024;             // hbmpc_dev_triplegen_parties: one launch (a workgroup per chunk of 2t + 1 triples) up to this many chunks (0: never)
     size_t fused_fpmul_max = 2048;                 // hbmpc_dev_fpmul_parties: one launch (a wave per element) up to this many elements (0: never)
     size_t fused_truncpr_max = 768;                // hbmpc_dev_truncpr_parties: the same (profiles/fused_truncpr_sweep.txt: ahead or level, eager and replayed)
+    size_t fused_mul_max = 1024;                   // hbmpc_dev_mul_parties: the same (profiles/fused_mul_sweep.txt: ahead both eager and replayed)
     bool gather_row_copies = false;                // hbmpc_dev_gather_party_major: take the per-row peer copies even where the 2-D copy applies (A/B aid)
     bool list_rows_in_kernel = true;               // the producers' mixing step writes the parties' lists itself (k_mfma_bfly<.., LISTS>)
     bool mfma_bfly = true;                         // large encodes take the domain points in pairs (kernels_mfma_bfly.hpp)
@@ -2250,3 +2252,4 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
 }
 
 #include "capi_truncpr.inc"
+#include "capi_mul.inc"

@@ -119,6 +119,9 @@ bool launch_fpmul_wave(const FpmulWaveArgs& a, int device, hipStream_t s, bool d
 // TruncPrNode / FPDivConstNode (a.w set) the same way (kernels_truncpr_wave.hpp); dry_run: only say whether the LDS layout fits
 struct TruncprWaveArgs;
 bool launch_truncpr_wave(const TruncprWaveArgs& a, int device, hipStream_t s, bool dry_run);
+// Multiply (Beaver) the same way (kernels_mul_wave.hpp)
+struct MulWaveArgs;
+bool launch_mul_wave(const MulWaveArgs& a, int device, hipStream_t s, bool dry_run);
 // flagged chunks: two cheap interpolation candidates before the OEC/Gao kernel (k_second_chance)
 void launch_second_chance(int impl, const SecondArgs& a, unsigned grid, hipStream_t s);
 bool launch_second_chance_m(int m, const SecondArgs& a, unsigned grid, hipStream_t s);  // U29, m = 2 .. 16 at compile time; false otherwise

@@ -75,6 +75,7 @@ def riss_tsets(n, t):
 
 
 FUSED_TRUNCPR_DEFAULT = 768  # hbmpc_set_fused_truncpr's default (csrc/hbmpc_capi.hip)
+FUSED_MUL_DEFAULT = 1024  # hbmpc_set_fused_mul's default (csrc/hbmpc_capi.hip)
 
 
 def fixed_point_reciprocal_scaled(denom, f):
@@ -554,6 +555,18 @@ class Engine:
     def set_fused_truncpr(self, max_elements: int):
         """hbmpc_dev_truncpr_parties is one launch up to this many batch elements (0: always three)"""
         assert self.L.hbmpc_set_fused_truncpr(self.ctx, C.c_size_t(max_elements)) == 0
+
+    def dev_mul_parties(self, sender_ids, a_d, b_d, c_d, x_d, y_d, N, n, t, de_ws_d, de_d, z_d, status_d=0, summary_d=0, stream=0):
+        """Multiply (Beaver) for all n parties of this device in one call (hbmpc_[gl_]dev_mul_parties; sender_ids are party ids): over
+        Fr one launch for a small batch, three otherwise; returns the ShareErrorCode"""
+        ids = (C.c_size_t * len(sender_ids))(*sender_ids)
+        return self._f("dev_mul_parties")(self.ctx, ids, C.c_size_t(len(sender_ids)), *(C.c_void_p(p) for p in (a_d, b_d, c_d, x_d, y_d)),
+                                          C.c_size_t(N), C.c_size_t(n), C.c_size_t(t),
+                                          *(C.c_void_p(p) for p in (de_ws_d, de_d, z_d, status_d, summary_d)), C.c_void_p(stream))
+
+    def set_fused_mul(self, max_elements: int):
+        """hbmpc_dev_mul_parties is one launch up to this many batch elements (0: always three)"""
+        assert self.L.hbmpc_set_fused_mul(self.ctx, C.c_size_t(max_elements)) == 0
 
     def dev_beaver_open_shares_paired(self, a_d, b_d, x_d, y_d, N, parties, de_d, stream=0):
         """de[party][0][N] = a - x, de[party][1][N] = b - y: one P(0) decode over 2 N values per sender opens both"""

@@ -12,6 +12,8 @@ in the library; this file only names things for the tests and bench.py.
   RanDouSha      DouShaNode::init_batch + RanDouShaNode::init_batch + reconstruction_handler + try_finalize
                  double_share/double_share_generation.rs:151-215, ran_dou_sha/mod.rs:371-449,569-602,314-331
   Preprocessing  run_preprocessing's triple part (honeybadger/mod.rs:1239-1393): RanSha -> a, b; RanDouSha -> r; TripleGen
+  Mul            Multiply (Beaver, RBC path): the opened shares, the open, finalize_mul
+                 honeybadger/mod.rs:543-628, mul/multiplication.rs:417-426,102-139,57-100
   TruncPr        TruncPrNode on its own                                      fpmul/truncpr.rs:185-318
   FpDivConst     FPDivConstNode: a * w for a public reciprocal w, then TruncPr   fpdiv/fpdiv_const.rs:61-99, fpdiv/mod.rs:8-60
   RandBit        RandBit: Beaver square of a, BatchRecon of a^2, phase 2   fpmul/rand_bit.rs:242-293,197-220
@@ -148,6 +150,27 @@ class FpMul(_Pipe):
 
     def download(self, which="out"):
         return self.download_named(which, (self.n, self.N))
+
+
+class Mul(_Pipe):
+    """Multiply (Beaver; honeybadger/mod.rs:543-628) of N element pairs for n parties, in either field: a - x and b - y opened by direct
+    robust interpolation, then finalize_mul.  Buffers x, y, ta, tb, tc, out are [party][N], desh [party][2][N], deop [2 N] (dop, eop:
+    its halves, [N] each), status 2 N bytes (chunk g: the a - x of element g, chunk N + g its b - y), summary the open's.
+    open_senders as in FpMul.  run() is one library call (hbmpc_[gl_]dev_mul_parties): over Fr ONE launch up to hbmpc_set_fused_mul
+    elements when the open has exactly 2t + 1 senders, three launches otherwise."""
+
+    def __init__(self, eng, n, t, N, stream=0, open_senders=None):
+        self.n, self.t, self.N = n, t, N
+        self.open_senders = 2 * t + 1 if open_senders is None else open_senders
+        super().__init__(eng, self._create(eng, "hbmpc_pipe_mul_create", n, t, N, self.open_senders, stream=stream), stream)
+
+    def upload(self, x, y, ta, tb, tc):
+        for name, src in (("x", x), ("y", y), ("ta", ta), ("tb", tb), ("tc", tc)):
+            self.upload_named(name, src)
+
+    def download(self, which="out"):
+        shape = {"deop": (2 * self.N,), "dop": (self.N,), "eop": (self.N,), "desh": (self.n, 2, self.N)}.get(which, (self.n, self.N))
+        return self.download_named(which, shape)
 
 
 class TruncPr(_Pipe):

@@ -313,6 +313,13 @@ impl GpuShares {
         let rc = unsafe { sys::hbmpc_pipe_fpmul_create(self.ctx, n, t, pairs, k, m, 0, stream, &mut p) };
         self.wrap(rc, p, n)
     }
+    /// `Multiply::init` for all n parties (honeybadger/mod.rs:543-628, mul/multiplication.rs:417-426,102-139,57-100; `mul_int`, :1177-1223,
+    /// wraps it): buffers x, y, ta, tb, tc ([party][pairs]), out = the shares of x * y
+    pub fn pipe_mul(&self, n: usize, t: usize, pairs: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_mul_create(self.ctx, n, t, pairs, 0, stream, &mut p) };
+        self.wrap(rc, p, n)
+    }
     /// `TruncPrNode` on its own for all n parties (fpmul/truncpr.rs:185-318): buffers a, rint ([party][values]), rbits ([party][m][values])
     pub fn pipe_truncpr(&self, n: usize, t: usize, values: usize, k: usize, m: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
         let mut p = std::ptr::null_mut();
