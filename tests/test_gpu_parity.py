@@ -392,7 +392,19 @@ def test_accumulator_headroom_adversarial(eng_all, n, t, d):
         rc, co, nco, st = e.batch_recover(ids, y, n, d, t)
         assert rc == rc0 and GU.eq(co, co0) and np.array_equal(st, st0) and np.array_equal(nco, nco0)
     S = min(n, d + 6)
-    rc, ci, deg = e.batch_interpolate(list(range(S)), np.ascontiguousarray(y[:S, : G // 2]), n) if False else (0, None, None)
+    # plain Lagrange through S >= d + 1 of the max-limb shares (`got` equals the uncorrupted y): the constant polynomials, every
+    # coefficient max-limb, every coefficient r - 1 -- per sampled column against the oracle.  Applies to every shape here.
+    ids, cols = list(range(S)), G // 2 + 20
+    ev = np.ascontiguousarray(got[:S, :cols])
+    rc, ci, deg = e.batch_interpolate(ids, ev, n)
+    assert rc == 0, e.last_error()
+    for g in (0, 1, G // 2 - 1, G // 2, G // 2 + 9, G // 2 + 10, cols - 1):
+        rc0, want, sec = O.nonrobust_recover_secret(ids, [S - 1] * S, ev[:, g], n)
+        assert rc0 == 0
+        pad = np.zeros((S, 4), dtype=np.uint64)
+        pad[: len(want)] = want
+        assert GU.eq(ci[g], pad) and deg[g] == max(len(want) - 1, 0), g
+        assert GU.eq(ci[g, : d + 1], x[g]) and not ci[g, d + 1:].any(), g
     bits = np.repeat(O.ints_to_u256([MAXLIMB, R - 1, 1, 0])[None, :, :], 40, axis=0)   # [m=40][N=4]
     assert GU.eq(e.truncpr_rdash(bits, 40)[1], O.truncpr_rdash(bits, 40)[1])
 
