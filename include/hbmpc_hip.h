@@ -231,7 +231,8 @@ ShareErrorCode hbmpc_pipe_ransha_create(hbmpc_ctx* ctx, size_t n, size_t t, size
 ShareErrorCode hbmpc_pipe_randousha_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t K, void* stream, hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_preprocessing_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream, hbmpc_pipe** pipe_out);
 /* RandBit (fpmul/rand_bit.rs:242-293, 197-220) over either field: N random bits for n parties from N shared values a and one Beaver
- * triple each.  N must be a multiple of t + 1 (rand_bit.rs:253-255: Incompatible; here InvalidInput), n >= 2t + 1.  run() is
+ * triple each.  N must be a multiple of t + 1 (rand_bit.rs:253-255: Incompatible; here InvalidInput), n >= 2t + 1.  run() is ONE call,
+ * hbmpc_[gl_]dev_randbit_parties on the handle's buffers: one launch for a small batch, and otherwise
  *   Multiply::init(a, a, triples) (mul/multiplication.rs:417-462): d = ta - a, e = tb - a side by side
  *       (hbmpc_[gl_]dev_beaver_open_shares_paired), opened by BatchRecon of degree t over the 2 N values: every party's encode
  *       (hbmpc_[gl_]dev_vandermonde_apply_parties), the recipients' P(0) decodes and the coefficient decode of the revealed values
@@ -245,7 +246,8 @@ ShareErrorCode hbmpc_pipe_preprocessing_create(hbmpc_ctx* ctx, size_t n, size_t 
  * bytes, the finalize's); summary (hbmpc_randbit_summary); desh ([n][2][N]); Y, Z, deop ([2 N]: d then e); the decodes' status
  * bytes and summaries rstatus_de, rstatus_sq ([n G] bytes), summary_de_first, summary_de, summary_sq_first, summary_sq (G: chunks
  * of the open).  hbmpc_pipe_summary reads summary_sq.  Checked mode returns the first failing decode's error, else HBMPC_ZERO_SQUARE
- * / HBMPC_NO_SQUARE_ROOT from the finalize's summary -- where the reference's `?` returns. */
+ * / HBMPC_NO_SQUARE_ROOT from the finalize's summary -- where the reference's `?` returns; it synchronises once, after the whole
+ * call, so a checked run that fails has run the later steps too.  Y and Z are workspaces: unspecified after a run. */
 ShareErrorCode hbmpc_pipe_randbit_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream, hbmpc_pipe** pipe_out);
 void hbmpc_pipe_destroy(hbmpc_pipe* pipe);
 ShareErrorCode hbmpc_pipe_part(hbmpc_pipe* pipe, const char* name, hbmpc_pipe** part_out);
@@ -899,6 +901,32 @@ ShareErrorCode hbmpc_dev_randbit_finalize_parties(hbmpc_ctx* ctx, const U256* a,
 ShareErrorCode hbmpc_gl_dev_randbit_finalize_parties(hbmpc_ctx* ctx, const uint64_t* a, const uint64_t* opened_sq, size_t N, size_t parties,
                                                      uint64_t* out, uint8_t* status_out, hbmpc_randbit_summary* summary_dev, void* stream);
 
+/* RandBit (fpmul/rand_bit.rs:242-293, 197-220) for all n parties of this device in one call: the Beaver square of a with one triple
+ * (ta, tb, tc) per element -- d = ta - a and e = tb - a opened by BatchRecon of degree t, finalize_mul -- BatchRecon of the [a^2]
+ * chunks of t + 1, phase 2.  Inputs a, ta, tb, tc [n][N].  Workspaces desh_ws [n][2][N] (receives the shares of d, then of e),
+ * y_ws [n n 2N/(t+1)] and z_ws [n 2N/(t+1)] (the opens' messages and revealed values: their contents after the call are unspecified
+ * in either form).  Outputs de_opened [2 N] (d, then e), sq_out [n][N] (the [a^2] shares), sq_opened [N], out [n][N] (the bit shares);
+ * status [N] bytes (phase 2's: 0 ok, 1 zero square, 2 no root; a failed element's shares are zero for every party), rstatus_de
+ * [n 2N/(t+1)] and rstatus_sq [n N/(t+1)] bytes (as the two decodes of an open leave them: [0, G) the revealed values' decode,
+ * [G, n G) recipients 1 .. n - 1 of the first).  summary_de_first, summary_de, summary_sq_first, summary_sq (device memory; may be
+ * NULL) and summary (required) as the separate calls write them.  Both opens decode from senders 0 .. 2t: a chunk that fails its
+ * verification opens to zero.  Refused with InvalidInput, before anything is written, unless N > 0 is a multiple of t + 1
+ * (rand_bit.rs:253-255), n is in 1 .. 255, n >= 2t + 1 and every required buffer is non-null.
+ * With at most hbmpc_set_fused_randbit chunks of t + 1 elements (default 256 over Fr, 1024 over Goldilocks), n <= 16 and t >= 1 the call is ONE launch, a workgroup per chunk
+ * (csrc/kernels_randbit_wg.hpp; a Sat32 context never takes it); otherwise the nine launches of hbmpc_pipe_randbit_create's list above.
+ * The same bytes in every output either way. */
+ShareErrorCode hbmpc_dev_randbit_parties(hbmpc_ctx* ctx, const U256* a, const U256* ta, const U256* tb, const U256* tc, size_t N, size_t n, size_t t,
+                                         U256* desh_ws, U256* y_ws, U256* z_ws, U256* de_opened, U256* sq_out, U256* sq_opened, U256* out,
+                                         uint8_t* status, uint8_t* rstatus_de, uint8_t* rstatus_sq, hbmpc_recover_summary* summary_de_first,
+                                         hbmpc_recover_summary* summary_de, hbmpc_recover_summary* summary_sq_first,
+                                         hbmpc_recover_summary* summary_sq, hbmpc_randbit_summary* summary, void* stream);
+ShareErrorCode hbmpc_gl_dev_randbit_parties(hbmpc_ctx* ctx, const uint64_t* a, const uint64_t* ta, const uint64_t* tb, const uint64_t* tc, size_t N,
+                                            size_t n, size_t t, uint64_t* desh_ws, uint64_t* y_ws, uint64_t* z_ws, uint64_t* de_opened,
+                                            uint64_t* sq_out, uint64_t* sq_opened, uint64_t* out, uint8_t* status, uint8_t* rstatus_de,
+                                            uint8_t* rstatus_sq, hbmpc_recover_summary* summary_de_first, hbmpc_recover_summary* summary_de,
+                                            hbmpc_recover_summary* summary_sq_first, hbmpc_recover_summary* summary_sq,
+                                            hbmpc_randbit_summary* summary, void* stream);
+
 /* ==== PRandBit / PRandInt: RISS-to-Shamir conversion (csrc/kernels_riss.hpp; fpmul/prandbitd.rs) ================================
  * PRandBitDNode<Goldilocks, Fr> lifts a Goldilocks bit to an Fr bit and a GF(2^8) bit (PRandBit) and makes Fr random integers
  * (PRandInt).  Every party sends a value r_T <= 2^(l+k) per maximal unqualified set T (the t-subsets of 0..n) to the parties outside
@@ -993,6 +1021,9 @@ ShareErrorCode hbmpc_set_fused_truncpr(hbmpc_ctx* ctx, size_t max_elements);
 /* hbmpc_dev_mul_parties runs as one launch up to max_elements batch elements (default 1024; 0: always the three separate
  * launches).  Same bytes either way (A/B aid). */
 ShareErrorCode hbmpc_set_fused_mul(hbmpc_ctx* ctx, size_t max_elements);
+/* hbmpc_[gl_]dev_randbit_parties runs as one launch up to max_chunks chunks of t + 1 elements (default 256 over Fr, 1024 over
+ * Goldilocks; 0: always the nine separate launches).  Same bytes either way (A/B aid). */
+ShareErrorCode hbmpc_set_fused_randbit(hbmpc_ctx* ctx, size_t max_chunks);
 /* hbmpc_dev_triplegen_parties runs as one launch up to max_chunks chunks of 2t + 1 triples (default 1024; 0: always the four
  * separate launches).  Same bytes either way (A/B aid). */
 ShareErrorCode hbmpc_set_fused_triplegen(hbmpc_ctx* ctx, size_t max_chunks);

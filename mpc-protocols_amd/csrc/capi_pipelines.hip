@@ -574,7 +574,6 @@ struct RandBit : hbmpc_pipe {
     uint8_t *status, *rst_de, *rst_sq;
     hbmpc_recover_summary *sm_de_first, *sm_de, *sm_sq_first;  // summ: summary_sq
     hbmpc_randbit_summary* rb;
-    std::vector<size_t> ids;
     RandBit(hbmpc_ctx* cx, size_t n_, size_t t_, size_t N_, void* s) : hbmpc_pipe(cx, s), n(n_), t(t_), N(N_) {
         if (n == 0 || N == 0 || N % (t + 1) != 0 || n < 2 * t + 1) throw PipeError{InvalidInput};  // rand_bit.rs:253-255
         Gde = 2 * N / (t + 1), Gsq = N / (t + 1);
@@ -594,38 +593,29 @@ struct RandBit : hbmpc_pipe {
         sm_de = reinterpret_cast<hbmpc_recover_summary*>(take_bytes("summary_de", 64, 16));
         sm_sq_first = reinterpret_cast<hbmpc_recover_summary*>(take_bytes("summary_sq_first", 64, 16));
         summ = reinterpret_cast<hbmpc_recover_summary*>(take_bytes("summary_sq", 64, 16));
-        for (size_t i = 0; i < 2 * t + 1; ++i) ids.push_back(i);
-    }
-    // BatchRecon (degree t) of x [party][G (t + 1)] -> opened [G (t + 1)] (batch_recon.rs:157-165, 384-391, 457-467)
-    void open(const unsigned char* x, size_t G, unsigned char* opened, uint8_t* st, hbmpc_recover_summary* first, hbmpc_recover_summary* second) {
-        PL(f.gl ? hbmpc_gl_dev_vandermonde_apply_parties(ctx, (const uint64_t*)x, G, n, t, n, (uint64_t*)Y, stream)
-                : hbmpc_dev_vandermonde_apply_parties(ctx, (const U256*)x, G, n, t, n, (U256*)Y, stream));
-        PL(f.recover_strided(ctx, ids.data(), ids.size(), Y, n * G, n * G, n, t, t, 1, Z, nullptr, st, first, stream));
-        check_summary(first);
-        PL(f.recover(ctx, ids.data(), ids.size(), Z, G, n, t, t, opened, nullptr, st, second, stream));
-        check_summary(second);
     }
     void run() override {
-        // Multiply::init(a, a, triples): d = ta - a, e = tb - a (multiplication.rs:417-426), opened together
-        PL(f.gl ? hbmpc_gl_dev_beaver_open_shares_paired(ctx, (const uint64_t*)ta, (const uint64_t*)tb, (const uint64_t*)a, (const uint64_t*)a, N, n,
-                                                         (uint64_t*)desh, stream)
-                : hbmpc_dev_beaver_open_shares_paired(ctx, (const U256*)ta, (const U256*)tb, (const U256*)a, (const U256*)a, N, n, (U256*)desh, stream));
-        open(desh, Gde, deop, rst_de, sm_de_first, sm_de);
-        // finalize_mul (multiplication.rs:57-100): [a^2] = tc - d e - d a - e a
-        const unsigned char* e = deop + N * f.eb;
-        PL(f.gl ? hbmpc_gl_dev_beaver_finalize_parties(ctx, (const uint64_t*)tc, (const uint64_t*)a, (const uint64_t*)a, (const uint64_t*)deop,
-                                                       (const uint64_t*)e, N, n, (uint64_t*)sq, stream)
-                : hbmpc_dev_beaver_finalize_parties(ctx, (const U256*)tc, (const U256*)a, (const U256*)a, (const U256*)deop, (const U256*)e, N, n,
-                                                    (U256*)sq, stream));
-        open(sq, Gsq, sqop, rst_sq, sm_sq_first, summ);  // rand_bit.rs:281-290
-        PL(f.gl ? hbmpc_gl_dev_randbit_finalize_parties(ctx, (const uint64_t*)a, (const uint64_t*)sqop, N, n, (uint64_t*)out, status, rb, stream)
-                : hbmpc_dev_randbit_finalize_parties(ctx, (const U256*)a, (const U256*)sqop, N, n, (U256*)out, status, rb, stream));
-        if (checked) {  // phase 2's `?` (rand_bit.rs:198-207)
-            hbmpc_randbit_summary v;
-            PL(hbmpc_memcpy_d2h(ctx, &v, rb, sizeof v, stream));
-            PL(hbmpc_stream_sync(ctx, stream));
-            if (v.n_failed != 0) throw PipeError{(v.first >> 32) == 1 ? HBMPC_ZERO_SQUARE : HBMPC_NO_SQUARE_ROOT};
-        }
+        // one call for the whole protocol: one launch for a small batch, nine otherwise (hbmpc_[gl_]dev_randbit_parties)
+        if (f.gl)
+            PL(hbmpc_gl_dev_randbit_parties(ctx, (const uint64_t*)a, (const uint64_t*)ta, (const uint64_t*)tb, (const uint64_t*)tc, N, n, t, (uint64_t*)desh,
+                                            (uint64_t*)Y, (uint64_t*)Z, (uint64_t*)deop, (uint64_t*)sq, (uint64_t*)sqop, (uint64_t*)out, status, rst_de, rst_sq,
+                                            sm_de_first, sm_de, sm_sq_first, summ, rb, stream));
+        else
+            PL(hbmpc_dev_randbit_parties(ctx, (const U256*)a, (const U256*)ta, (const U256*)tb, (const U256*)tc, N, n, t, (U256*)desh, (U256*)Y, (U256*)Z,
+                                         (U256*)deop, (U256*)sq, (U256*)sqop, (U256*)out, status, rst_de, rst_sq, sm_de_first, sm_de, sm_sq_first, summ, rb,
+                                         stream));
+        if (!checked) return;
+        // the opens' `?` in their order, then phase 2's (rand_bit.rs:198-207): the first summary that failed decides, read after ONE
+        // synchronisation (the later steps have run by then)
+        hbmpc_recover_summary v[4];
+        hbmpc_randbit_summary r;
+        hbmpc_recover_summary* const order[4] = {sm_de_first, sm_de, sm_sq_first, summ};
+        for (int i = 0; i < 4; ++i) PL(hbmpc_memcpy_d2h(ctx, &v[i], order[i], sizeof v[i], stream));
+        PL(hbmpc_memcpy_d2h(ctx, &r, rb, sizeof r, stream));
+        PL(hbmpc_stream_sync(ctx, stream));
+        for (int i = 0; i < 4; ++i)
+            if (v[i].n_failed != 0) throw PipeError{(ShareErrorCode)v[i].first_error};
+        if (r.n_failed != 0) throw PipeError{(r.first >> 32) == 1 ? HBMPC_ZERO_SQUARE : HBMPC_NO_SQUARE_ROOT};
     }
 };
 

@@ -9,9 +9,10 @@ struct SortedSenders {
 };
 
 // validation order of robust_interpolate.rs:290-341
+// honest_majority: the caller has checked n >= 2t + 1 itself (RandBit's opens, capi_randbit.inc: exactly 2t + 1 senders, no OEC round)
 ShareErrorCode validate_senders(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, size_t G, size_t n, size_t d,
-                                size_t t, SortedSenders* out) {
-    if (n < 3 * t + 1) return fail(ctx, InvalidInput, "n must be >= 3t + 1 for Byzantine fault tolerance");
+                                size_t t, SortedSenders* out, bool honest_majority = false) {
+    if (n < (honest_majority ? 2 : 3) * t + 1) return fail(ctx, InvalidInput, "n must be >= 3t + 1 for Byzantine fault tolerance");
     if (S == 0) return fail(ctx, InvalidInput, "No evaluations provided");
     if (G == 0) return fail(ctx, InvalidInput, "Empty batch");
     std::vector<std::pair<size_t, int>> v(S);
@@ -161,6 +162,7 @@ struct RecoverCall {
     const PairInput* pair = nullptr;
     int only_coeff = 0, second_coeff = -1;
     size_t group = 0, group_stride = 0;  // group q's values q * group_stride elements further on in every sender row (RecoverArgs::group)
+    bool honest_majority = false;        // n >= 2t + 1 is enough (validate_senders)
 };
 
 // the decode's table of a sender set: the verify rows (vm), then the coefficient rows (bc)
@@ -305,7 +307,7 @@ ShareErrorCode batch_recover_dev(hbmpc_ctx* ctx, RecoverCall c) {
     sh.slots = c.slots != nullptr, sh.pair = c.pair != nullptr, sh.pair_N = c.pair ? c.pair->N : 0, sh.host_call = c.host_call;
     if (recover_cover(k, sh, true) != RecoverCover::Run) return HBMPC_NOT_FUSED;
     SortedSenders ss;
-    ShareErrorCode rc = validate_senders(ctx, c.sender_ids, S, G, n, d, c.second_coeff >= 0 ? 0 : t, &ss);
+    ShareErrorCode rc = validate_senders(ctx, c.sender_ids, S, G, n, d, c.second_coeff >= 0 ? 0 : t, &ss, c.honest_majority);
     if (rc != ShareSuccess) return rc;
     if (n > 255) return fail(ctx, InvalidInput, "n > 255 (HoneyBadgerMPCNodeOpts limits n to 255)");
     if (c.slots)

@@ -22,6 +22,7 @@
 #include "kernels_truncpr_wave.hpp"
 #include "kernels_mul_wave.hpp"
 #include "kernels_triplegen_wg.hpp"
+#include "kernels_randbit_wg.hpp"
 #include "launchers.hpp"
 #include "tables.hpp"
 #include "tables_mfma.hpp"
@@ -35,6 +36,10 @@
 
 using namespace hbmpc;
 
+// hbmpc_[gl_]dev_randbit_parties as one launch: the defaults of hbmpc_set_fused_randbit per field, in chunks of t + 1 elements -- the
+// largest swept size at which one launch measured ahead of or level with the nine, eager and replayed, at n = 16 and at n = 4
+// (profiles/fused_randbit_sweep.txt; over Fr each element's 255-bit exponentiation runs on a single lane in either form)
+constexpr size_t FUSED_RANDBIT_FR = 256, FUSED_RANDBIT_GL = 1024;
 constexpr size_t STAGE_PIN_BLOCK = (size_t)2048 << 10;  // pinned host block of the small-call staging path (Stage, hbmpc_scrub_staging)
 struct hbmpc_ctx {
     int device = 0;
@@ -74,6 +79,7 @@ struct hbmpc_ctx {
     size_t fused_fpmul_max = 2048;                 // hbmpc_dev_fpmul_parties: one launch (a wave per element) up to this many elements (0: never)
     size_t fused_truncpr_max = 768;                // hbmpc_dev_truncpr_parties: the same (profiles/fused_truncpr_sweep.txt: ahead or level, eager and replayed)
     size_t fused_mul_max = 1024;                   // hbmpc_dev_mul_parties: the same (profiles/fused_mul_sweep.txt: ahead both eager and replayed)
+    size_t fused_randbit_max = FUSED_RANDBIT_FR;   // hbmpc_dev_randbit_parties: one launch (a workgroup per chunk of t + 1 elements) up to this many chunks (0: never); per field, hbmpc_create
     bool gather_row_copies = false;                // hbmpc_dev_gather_party_major: take the per-row peer copies even where the 2-D copy applies (A/B aid)
     bool list_rows_in_kernel = true;               // the producers' mixing step writes the parties' lists itself (k_mfma_bfly<.., LISTS>)
     bool mfma_bfly = true;                         // large encodes take the domain points in pairs (kernels_mfma_bfly.hpp)
@@ -347,7 +353,7 @@ extern "C" ShareErrorCode hbmpc_create(int device, FieldKind field_kind, hbmpc_c
     }
     const char* env = getenv("HBMPC_FIELD_IMPL");
     if (env && std::string(env) == "sat32") ctx->impl = IMPL_SAT32;
-    if (field_kind == Goldilocks64) ctx->impl = IMPL_GOLD;
+    if (field_kind == Goldilocks64) ctx->impl = IMPL_GOLD, ctx->fused_randbit_max = FUSED_RANDBIT_GL;
     env = getenv("HBMPC_MATRIX_CORES");
     if (env && std::string(env) == "0") ctx->matrix_cores = false;
     hipDeviceProp_t prop;
@@ -2253,3 +2259,4 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
 
 #include "capi_truncpr.inc"
 #include "capi_mul.inc"
+#include "capi_randbit.inc"

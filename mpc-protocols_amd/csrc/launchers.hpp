@@ -115,6 +115,8 @@ void launch_recover_wide(int impl, bool p0, const RecoverArgs& ra, const SecondA
 struct FpmulWaveArgs;
 struct TripleGenWgArgs;
 void launch_triplegen_wg(int impl, const TripleGenWgArgs& a, hipStream_t s);  // TripleGenNode, a workgroup per chunk (kernels_triplegen_wg.hpp): U29 or Goldilocks
+struct RandBitWgArgs;
+void launch_randbit_wg(int impl, const RandBitWgArgs& a, hipStream_t s);  // RandBit, a workgroup per chunk of t + 1 elements (kernels_randbit_wg.hpp): U29 or Goldilocks
 bool launch_fpmul_wave(const FpmulWaveArgs& a, int device, hipStream_t s, bool dry_run);
 // TruncPrNode / FPDivConstNode (a.w set) the same way (kernels_truncpr_wave.hpp); dry_run: only say whether the LDS layout fits
 struct TruncprWaveArgs;

@@ -76,6 +76,7 @@ def riss_tsets(n, t):
 
 FUSED_TRUNCPR_DEFAULT = 768  # hbmpc_set_fused_truncpr's default (csrc/hbmpc_capi.hip)
 FUSED_MUL_DEFAULT = 1024  # hbmpc_set_fused_mul's default (csrc/hbmpc_capi.hip)
+FUSED_RANDBIT_DEFAULT = {"fr": 256, "goldilocks": 1024}  # hbmpc_set_fused_randbit's default per field (FUSED_RANDBIT_FR / _GL, csrc/hbmpc_capi.hip)
 
 
 def fixed_point_reciprocal_scaled(denom, f):
@@ -602,6 +603,19 @@ class Engine:
         (status << 32) | index, u32 n_failed); returns the ShareErrorCode"""
         return self._f("dev_randbit_finalize_parties")(self.ctx, C.c_void_p(a_d), C.c_void_p(sq_d), C.c_size_t(N), C.c_size_t(parties),
                                                          C.c_void_p(out_d), C.c_void_p(status_d), C.c_void_p(summary_d), C.c_void_p(stream))
+
+    def randbit_parties(self, a_d, ta_d, tb_d, tc_d, N, n, t, desh_d, y_d, z_d, deop_d, sq_d, sqop_d, out_d, status_d, rstatus_de_d, rstatus_sq_d,
+                        summary_de_first_d=0, summary_de_d=0, summary_sq_first_d=0, summary_sq_d=0, summary_d=0, stream=0):
+        """RandBit for all n parties of this device in one call (hbmpc_[gl_]dev_randbit_parties; device pointers): one launch up to
+        hbmpc_set_fused_randbit chunks of t + 1 elements when n <= 16, nine otherwise; returns the ShareErrorCode"""
+        return self._f("dev_randbit_parties")(self.ctx, *(C.c_void_p(p) for p in (a_d, ta_d, tb_d, tc_d)), C.c_size_t(N), C.c_size_t(n), C.c_size_t(t),
+                                              *(C.c_void_p(p) for p in (desh_d, y_d, z_d, deop_d, sq_d, sqop_d, out_d, status_d, rstatus_de_d,
+                                                                        rstatus_sq_d, summary_de_first_d, summary_de_d, summary_sq_first_d,
+                                                                        summary_sq_d, summary_d)), C.c_void_p(stream))
+
+    def set_fused_randbit(self, max_chunks: int):
+        """hbmpc_[gl_]dev_randbit_parties is one launch up to this many chunks of t + 1 elements (0: always nine)"""
+        assert self.L.hbmpc_set_fused_randbit(self.ctx, C.c_size_t(max_chunks)) == 0
 
     # ---- PRandBit / PRandInt: RISS fold, RISS-to-Shamir conversion, finalize (csrc/kernels_riss.hpp) ----
     FIELD_CAPACITY = 104  # HBMPC_FIELD_CAPACITY

@@ -309,7 +309,8 @@ class RandBit(_Pipe):
     multiple of t + 1).  Buffers a, ta, tb, tc, out, sq are [party][N]; sqop [N] the opened squares; status [N] bytes and summary
     (u64 first, u32 n_failed) the finalize's; rstatus_de / rstatus_sq and summary_de_first, summary_de, summary_sq_first,
     summary_sq the four decodes'.  run(check=True) raises with HBMPC_ZERO_SQUARE (102) / HBMPC_NO_SQUARE_ROOT (103) where
-    phase 2's `?` returns, or with a failed open's error."""
+    phase 2's `?` returns, or with a failed open's error.  run() is one library call (hbmpc_[gl_]dev_randbit_parties): ONE launch up to
+    hbmpc_set_fused_randbit chunks of t + 1 elements when n <= 16 (256 over Fr, 1 024 over Goldilocks), nine launches beyond."""
 
     ZERO_SQUARE, NO_SQUARE_ROOT = 102, 103
 

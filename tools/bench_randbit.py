@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """RandBit timing: the phase-2 kernel (hbmpc_[gl_]dev_randbit_finalize_parties) from device events, and the whole pipeline
-(hbmpc_pipe_randbit_create) eager and replayed as a HIP graph.  One JSON line per (field, n, N), with the bytes the finalize moves,
+(hbmpc_pipe_randbit_create) eager and replayed as a HIP graph, in both forms of hbmpc_[gl_]dev_randbit_parties: ONE launch (forced by
+hbmpc_set_fused_randbit; not timed beyond --one-max chunks) and the nine launches (threshold 0).  One JSON line per (field, n, N), with the bytes the finalize moves,
 its modular multiplications per element and the two floors they give:
   bytes / 4.2-5.0 TB/s  (the measured mixed read/write stream band, profiles/r04_hbm_mix_ubench.txt)
   multiplications / 1.85e11 per second  (register-resident Fr modmul rate; Goldilocks' mulm is far cheaper,
@@ -53,6 +54,7 @@ def main():
     ap.add_argument("--t", type=int, default=5)
     ap.add_argument("--sizes", default=str(1 << 20) + ",1024")
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--one-max", type=int, default=16384, help="the one-launch form is not timed beyond this many chunks of t + 1 elements")
     args = ap.parse_args()
     import torch
     from __graft_entry__ import load_package
@@ -88,17 +90,26 @@ def main():
             ptr = {k: rb.buffer(k)[0] for k in ("a", "sqop", "out", "status", "summary")}
             fin = lambda: eng.randbit_finalize_parties(ptr["a"], ptr["sqop"], N, n, ptr["out"], ptr["status"], ptr["summary"], st)  # noqa: E731
             ms_fin = timed(fin)
-            ms_eager = timed(lambda: rb.run(check=False))
-            rb.capture()
-            ms_graph = timed(rb.replay)
-            assert not rb.status().any()
+            forms = {}
+            for form, fused in (("one", 1 << 30), ("nine", 0)):
+                if form == "one" and N // (t + 1) > args.one_max:
+                    forms[form] = (None, None)
+                    continue
+                eng.set_fused_randbit(fused)
+                ms_eager = timed(lambda: rb.run(check=False))
+                rb.capture()  # records the form that the threshold selects now
+                forms[form] = (round(ms_eager, 4), round(timed(rb.replay), 4))
+                assert not rb.status().any()
+            eng.set_fused_randbit(pkg.hbmpc.FUSED_RANDBIT_DEFAULT[field])
             eb = eng.ebytes
             nbytes = (1 + 2 * n) * N * eb + N
             muls = muls_per_element(p, n)
             floor_hbm = [nbytes / bw * 1e3 for bw in HBM_BAND[::-1]]
             floor_alu = muls * N / FR_MODMUL_RATE * 1e3
-            print(json.dumps({"field": field, "n": n, "t": t, "N": N, "finalize_ms": round(ms_fin, 4), "pipeline_eager_ms": round(ms_eager, 4),
-                              "pipeline_graph_ms": round(ms_graph, 4), "finalize_bytes": nbytes, "modmul_per_element": muls,
+            print(json.dumps({"field": field, "n": n, "t": t, "N": N, "finalize_ms": round(ms_fin, 4),
+                              "pipeline_one_launch_ms": {"eager": forms["one"][0], "graph": forms["one"][1]},
+                              "pipeline_nine_launches_ms": {"eager": forms["nine"][0], "graph": forms["nine"][1]},
+                              "finalize_bytes": nbytes, "modmul_per_element": muls,
                               "floor_hbm_ms": [round(x, 4) for x in floor_hbm], "floor_modmul_ms": round(floor_alu, 4),
                               "finalize_over_floor": round(ms_fin / max(floor_hbm[1], floor_alu if field == "fr" else 0.0), 2)}), flush=True)
             rb.close()
