@@ -2,7 +2,7 @@
 //   <call> <knobs> <field> <G> <n> <d> <parties>
 // call: shares (chunk-major; parties > 1: vandermonde_apply_parties), strided (chunk-major, an output row stride), rows, lists
 // (rows writing the producers' lists), triple, triple_ws (triple with a workspace).  knobs: a comma-separated list of the knob
-// settings the tests use (default, mc0 .. mc3, min1, generic, fusion0, small0, wgs8).  field: fr, sat32, gl.
+// settings the tests use (default, mc0 .. mc3, min<N>, generic, fusion0, small0, wgs8).  field: fr, sat32, gl.
 // One line out per query: the first route, "kernel M=<d + 1> rows=<rows per role> roles=<roles> <one|per-party>" (a route through
 // the workspace names the chunk-major route it continues with after '>'), then " lists_in_kernel=<0|1>" for lists calls and
 // " all=" with every candidate in order.
@@ -67,8 +67,9 @@ int main() {
             if (!strncmp(tok, "mc", 2)) {  // hbmpc_set_matrix_cores(on, 0)
                 const int on = atoi(tok + 2);
                 k.matrix_cores = on != 0, k.mfma_team = on != 2, k.mfma_bfly = on != 3;
-            } else if (!strcmp(tok, "min1")) {  // hbmpc_set_matrix_cores(.., min_chunks = 1)
-                k.mfma_min_encode = 1, k.mfma_min_gold = 1;
+            } else if (!strncmp(tok, "min", 3) && atoi(tok + 3) > 0) {  // hbmpc_set_matrix_cores(.., min_chunks = N)
+                const size_t mn = (size_t)atoi(tok + 3);
+                k.mfma_min_encode = mn < 2049 ? mn : 2049, k.mfma_min_gold = mn < 4096 ? mn : 4096;
             } else if (!strcmp(tok, "generic")) {
                 k.force_generic = true;
             } else if (!strcmp(tok, "fusion0")) {

@@ -1,7 +1,10 @@
 // CPU-only dump of the host-side table builders (mpc-protocols_amd/csrc/tables.hpp, host_fr.hpp) for
 // tests/test_host_tables.py, which compares every value with the big-int oracle.  Built with
 // -fsanitize=address,undefined: the table code is the only host arithmetic in the product.
-//   usage: host_tables_dump <fr|gl> <n> <d> <t> <id0,id1,...>
+//   usage: host_tables_dump <fr|gl> <n> <d> <t> <id0,id1,...> [full]
+// full: the matrix-core tables are printed whatever their size, and so are the tables of the other instances -- enc (one row per point),
+// bflyR (point pairs, rows alpha^i 2^261: triple generation), bflyinv (point pairs of the inverse transform on a full domain)
+// (tests/test_mfma_inputs.py compares each byte for byte with the integer model of tests/mfma_model.py)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,8 +24,13 @@ static void put(const char* tag, const H& v) {
     std::printf("%s %016llx%016llx%016llx%016llx\n", tag, (unsigned long long)c[3], (unsigned long long)c[2], (unsigned long long)c[1],
                 (unsigned long long)c[0]);
 }
+static void put_words(const char* tag, const std::vector<uint32_t>& tab) {
+    std::printf("%s", tag);
+    for (uint32_t x : tab) std::printf(" %08x", x);
+    std::printf("\n");
+}
 template <class H>
-static int run(size_t n, size_t d, size_t t, const std::vector<size_t>& ids) {
+static int run(size_t n, size_t d, size_t t, const std::vector<size_t>& ids, bool full) {
     const size_t m = d + 1, needed = d + t + 1;
     H w;
     if (!domain_omega(domain_size(n), &w)) return 2;
@@ -67,11 +75,17 @@ static int run(size_t n, size_t d, size_t t, const std::vector<size_t>& ids) {
         if constexpr (std::is_same<H, HGl>::value) tab = build_mfma_table_gl(rows, m);
         else tab = build_mfma_table(rows, m);
         std::printf("mfma_bytes %zu\n", tab.size() * 4);
-        if (tab.size() * 4 <= 65536) {
-            std::printf("mfma");
-            for (uint32_t x : tab) std::printf(" %08x", x);
-            std::printf("\n");
+        if (full || tab.size() * 4 <= 65536) put_words("mfma", tab);
+    }
+    // full: the encode's table with one row per point
+    if (full && m >= 2 && m <= (std::is_same<H, HGl>::value ? MFGL_MAX_M : MF_MAX_M)) {
+        std::vector<std::vector<H>> V(n, std::vector<H>(m));
+        for (size_t j = 0; j < n; ++j) {
+            H p = H::one();
+            for (size_t k = 0; k < m; ++k) V[j][k] = p, p = p * el[j];
         }
+        if constexpr (std::is_same<H, HGl>::value) put_words("enc", build_mfma_table_gl(V, m));
+        else put_words("enc", build_mfma_table(V, m));
     }
     // the point-pair table of the matrix-core encode (tables_mfma.hpp::build_mfma_bfly_table) for y = X * V on this domain
     if constexpr (std::is_same<H, HFr>::value) {
@@ -84,11 +98,22 @@ static int run(size_t n, size_t d, size_t t, const std::vector<size_t>& ids) {
             const size_t half = domain_size(n) / 2;
             const auto tab = build_mfma_bfly_table(V, m, half);
             std::printf("bfly_bytes %zu\n", tab.size() * 4);
-            if (tab.size() * 4 <= 140000) {
-                std::printf("bfly");
-                for (uint32_t x : tab) std::printf(" %08x", x);
-                std::printf("\n");
+            if (full || tab.size() * 4 <= 140000) put_words("bfly", tab);
+            if (full && m <= MF_MAX_M) {  // triple generation: the same rows times the Montgomery radix 2^261
+                HFr R = HFr::one();
+                const HFr two = HFr::from_u64(2);
+                for (int e = 0; e < 261; ++e) R = R * two;
+                for (auto& row : V)
+                    for (auto& v : row) v = v * R;
+                put_words("bflyR", build_mfma_bfly_table(V, m, half));
             }
+        }
+        if (full && n == domain_size(n) && n >= 8 && n <= MF_BFLY_MAX_M) {  // the inverse transform: omega^(-i k) / n
+            const HFr ninv = HFr::from_u64(n).inv();
+            std::vector<std::vector<HFr>> C(n, std::vector<HFr>(n));
+            for (size_t i = 0; i < n; ++i)
+                for (size_t k = 0; k < n; ++k) C[i][k] = el[(n - (i * k) % n) % n] * ninv;
+            put_words("bflyinv", build_mfma_bfly_table(C, n, n / 2));
         }
     }
     return 0;
@@ -99,5 +124,6 @@ int main(int argc, char** argv) {
     std::vector<size_t> ids;
     for (char* p = std::strtok(argv[5], ","); p; p = std::strtok(nullptr, ",")) ids.push_back(std::strtoul(p, nullptr, 10));
     if (ids.size() < d + t + 1) return 1;
-    return std::strcmp(argv[1], "gl") == 0 ? run<HGl>(n, d, t, ids) : run<HFr>(n, d, t, ids);
+    const bool full = argc > 6 && std::strcmp(argv[6], "full") == 0;
+    return std::strcmp(argv[1], "gl") == 0 ? run<HGl>(n, d, t, ids, full) : run<HFr>(n, d, t, ids, full);
 }

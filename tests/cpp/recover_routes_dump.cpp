@@ -3,7 +3,7 @@
 // call: dev (a device-pointer call), host (a host-pointer call), p0, p0_host, coeff<k> (P(0)-shaped, coefficient k), top<k>_group<g>
 // (coefficient k, groups of g chunks), sel<a>_<b> (select-two: coefficients a and b), sel<a>_<b>_group<g>, slots, pair<N> (the fpmul
 // pair form over N elements per half), interp, interp_deg, interp_c0 (batch_interpolate_dev without / with degrees / with c0 and
-// degrees; S points of n, G chunks).  knobs: a comma-separated list of the knob settings the tests use (default, mc0 .. mc2, min1,
+// degrees; S points of n, G chunks).  knobs: a comma-separated list of the knob settings the tests use (default, mc0 .. mc2, min<N>,
 // generic, small0, wgs8, single0, second0, lazy0 .. lazy2, fusion0).  field: fr, sat32, gl.  facts: a comma-separated list of
 // capturing, cached, or "-".
 // One line out per query: "notfused-early", "notfused", "single-invalid", or the plan:
@@ -74,8 +74,10 @@ int main() {
             if (!strncmp(tok, "mc", 2)) {  // hbmpc_set_matrix_cores(on, 0)
                 const int on = atoi(tok + 2);
                 k.matrix_cores = on != 0, k.mfma_team = on != 2, k.mfma_bfly = on != 3;
-            } else if (!strcmp(tok, "min1")) {  // hbmpc_set_matrix_cores(.., min_chunks = 1)
-                k.mfma_min_cached = k.mfma_min_direct = k.mfma_min_gold_direct = k.mfma_min_gold_oec = 1;
+            } else if (!strncmp(tok, "min", 3) && atoi(tok + 3) > 0) {  // hbmpc_set_matrix_cores(.., min_chunks = N)
+                const size_t mn = (size_t)atoi(tok + 3);
+                k.mfma_min_cached = mn < 4096 ? mn : 4096, k.mfma_min_direct = k.mfma_min_gold_direct = mn < 2048 ? mn : 2048;
+                k.mfma_min_gold_oec = mn < 8193 ? mn : 8193;
             } else if (!strcmp(tok, "generic")) {
                 k.force_generic = true;
             } else if (!strcmp(tok, "small0")) {
