@@ -1,12 +1,6 @@
 // capi_randbit.inc -- RandBit for all parties on this device (fpmul/rand_bit.rs:242-293, 197-220; honeybadger/mod.rs:1951-2086)
 // (included at the end of hbmpc_capi.hip).
 
-extern "C" ShareErrorCode hbmpc_set_fused_randbit(hbmpc_ctx* ctx, size_t max_chunks) {
-    if (!ctx) return InvalidInput;
-    ctx->fused_randbit_max = max_chunks;
-    return ShareSuccess;
-}
-
 namespace {
 
 // every buffer of the call, typed per field by the two entry points
@@ -25,8 +19,7 @@ struct RandBitCall {
 // coefficient decode of the revealed values from the same.
 ShareErrorCode randbit_launches(hbmpc_ctx* ctx, const RandBitCall& c) {
     const size_t N = c.N, n = c.n, t = c.t, Gde = 2 * N / (t + 1), Gsq = N / (t + 1), eb = ebytes(ctx);
-    std::vector<size_t> ids(2 * t + 1);
-    for (size_t i = 0; i < ids.size(); ++i) ids[i] = i;
+    const std::vector<size_t> ids = first_ids(2 * t + 1);
     // BatchRecon (degree t) of x [party][G (t + 1)] -> opened [G (t + 1)] (batch_recon.rs:157-165, 384-391, 457-467)
     auto open = [&](const void* x, size_t G, void* opened, uint8_t* st, hbmpc_recover_summary* first, hbmpc_recover_summary* second) -> ShareErrorCode {
         ShareErrorCode rc = eval_dev(ctx, x, G, n, t, c.Y, c.stream, n);
@@ -53,25 +46,19 @@ ShareErrorCode randbit_launches(hbmpc_ctx* ctx, const RandBitCall& c) {
 // H: HFr or HGl.  All of the validation comes before the first launch or memset: a call that is refused has written nothing.
 template <class H>
 ShareErrorCode randbit_parties_any(hbmpc_ctx* ctx, const RandBitCall& c) {
-    constexpr bool gold = std::is_same<H, HGl>::value;
     const size_t N = c.N, n = c.n, t = c.t;
     if (!c.a || !c.ta || !c.tb || !c.tc || !c.desh || !c.Y || !c.Z || !c.deop || !c.sq || !c.sqop || !c.out || !c.status || !c.rst_de || !c.rst_sq || !c.rb)
         return fail(ctx, InvalidInput, "null buffer");
-    if (N == 0 || n == 0 || n > 255) return fail(ctx, InvalidInput, "N, n out of range");
+    if (!batch_in_range(ctx, N, n)) return InvalidInput;
     if (t >= n || N % (t + 1) != 0) return fail(ctx, InvalidInput, "N must be a multiple of t + 1");  // rand_bit.rs:253-255
     if (n < 2 * t + 1) return fail(ctx, InvalidInput, "n must be >= 2t + 1");
-    const size_t G = N / (t + 1);
-    // Small batches: one launch, a workgroup per chunk of t + 1 elements (kernels_randbit_wg.hpp).  Both opens decode from exactly
-    // 2t + 1 senders (no OEC round), and the (party, recipient) pairs of one open fit the workgroup.
-    if (G <= ctx->fused_randbit_max && n <= 16 && t >= 1 && (gold || ctx->impl == IMPL_U29) && !ctx->force_generic && ctx->direct_fail) {
+    if (plan_protocol(protocol_knobs(ctx), {ProtocolCall::RandBit, N, n, t, 0, 0}).one_launch) {  // a workgroup per chunk of t + 1 elements (kernels_randbit_wg.hpp)
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         hipStream_t s = pick(ctx, c.stream);
         const int impl = ctx->impl;
         RandBitWgArgs ra;
         memset(&ra, 0, sizeof ra);
-        std::vector<size_t> ids(2 * t + 1);
-        for (size_t i = 0; i < ids.size(); ++i) ids[i] = i;
-        ShareErrorCode rc = rec_table<H>(ctx, *domain_inv<H>(ctx, n), ids, n, t, t, &ra.tab);
+        ShareErrorCode rc = rec_table<H>(ctx, *domain_inv<H>(ctx, n), first_ids(2 * t + 1), n, t, t, &ra.tab);
         if (rc != ShareSuccess) return rc;
         rc = vmat_table<H>(ctx, n, t, &ra.vmat);
         if (rc != ShareSuccess) return rc;
@@ -81,30 +68,24 @@ ShareErrorCode randbit_parties_any(hbmpc_ctx* ctx, const RandBitCall& c) {
         memcpy(ra.r2, cs.r2, sizeof ra.r2);
         ra.a = as_words(c.a), ra.ta = as_words(c.ta), ra.tb = as_words(c.tb), ra.tc = as_words(c.tc);
         ra.desh = as_words(c.desh), ra.deop = as_words(c.deop), ra.sq = as_words(c.sq), ra.sqop = as_words(c.sqop), ra.out = as_words(c.out);
-        ra.status = c.status, ra.rst_de = c.rst_de, ra.rst_sq = c.rst_sq;
-        ra.rb = reinterpret_cast<RandBitSummaryDev*>(c.rb);
+        ra.status = c.status, ra.rst_de = c.rst_de, ra.rst_sq = c.rst_sq, ra.rb = reinterpret_cast<RandBitSummaryDev*>(c.rb);
         ra.N = N, ra.n = (int)n, ra.t = (int)t;
-        return with_decode_counters(ctx, s, 2048, [&](uint32_t* counters) -> ShareErrorCode {
-            ra.counters = counters;
-            ra.sm_de_first = c.sm_de_first ? (uint32_t*)c.sm_de_first : counters + 4;  // the scratch's local summary slot
-            ra.sm_de = c.sm_de ? (uint32_t*)c.sm_de : counters + 4;
-            ra.sm_sq_first = c.sm_sq_first ? (uint32_t*)c.sm_sq_first : counters + 4;
-            ra.sm_sq = c.sm_sq ? (uint32_t*)c.sm_sq : counters + 4;
-            HIP_TRY(ctx, hipMemsetAsync(c.rb, 0xff, 8, s));  // first = all ones
-            HIP_TRY(ctx, hipMemsetAsync((char*)c.rb + 8, 0, 8, s));
-            launch_randbit_wg(impl, ra, s);
-            HIP_TRY(ctx, hipGetLastError());
-            return ShareSuccess;  // the kernel's last workgroup leaves the counters at zero
-        });
+        return enqueue_one_launch(ctx, s, &ra.counters, {{&ra.sm_de_first, c.sm_de_first}, {&ra.sm_de, c.sm_de}, {&ra.sm_sq_first, c.sm_sq_first}, {&ra.sm_sq, c.sm_sq}},
+                                  [&]() -> ShareErrorCode {
+                                      HIP_TRY(ctx, hipMemsetAsync(c.rb, 0xff, 8, s));  // first = all ones
+                                      HIP_TRY(ctx, hipMemsetAsync((char*)c.rb + 8, 0, 8, s));
+                                      launch_randbit_wg(impl, ra, s);
+                                      return ShareSuccess;
+                                  });
     }
     return randbit_launches(ctx, c);
 }
 
 }  // namespace
 
-// The call is ONE launch for a small batch (kernels_randbit_wg.hpp), and otherwise hbmpc_dev_beaver_open_shares_paired, the encode and
-// the two decodes of d and e, hbmpc_dev_beaver_finalize_parties, the same three of a^2 and hbmpc_dev_randbit_finalize_parties -- the
-// same bytes in every output buffer.
+// The call is ONE launch (kernels_randbit_wg.hpp), or hbmpc_dev_beaver_open_shares_paired, the encode and the two decodes of d and
+// e, hbmpc_dev_beaver_finalize_parties, the same three of a^2 and hbmpc_dev_randbit_finalize_parties -- the same bytes in every
+// output buffer.  Which: plan_protocol (protocol_route.hpp).
 #define TYPED_RANDBIT(T, H, REQ, PFX)                                                                                                          \
     extern "C" ShareErrorCode PFX##dev_randbit_parties(hbmpc_ctx* ctx, const T* a, const T* ta, const T* tb, const T* tc, size_t N, size_t n,   \
                                                        size_t t, T* desh_ws, T* y_ws, T* z_ws, T* de_opened, T* sq_out, T* sq_opened, T* out,   \

@@ -142,6 +142,11 @@ RecoverKnobs recover_knobs(const hbmpc_ctx* ctx) {
                         ctx->list_rows_in_kernel, ctx->lazy_fallback_tables, ctx->wide_max_chunks, ctx->mfma_min_cached, ctx->mfma_min_direct,
                         ctx->mfma_min_gold_direct, ctx->mfma_min_gold_oec, ctx->mfma_wgs, ctx->n_cus};
 }
+// ... and of the protocol calls' rule (protocol_route.hpp)
+ProtocolKnobs protocol_knobs(const hbmpc_ctx* ctx) {
+    return ProtocolKnobs{ctx->impl, ctx->force_generic, ctx->direct_fail, ctx->fused_triplegen_max, ctx->fused_fpmul_max, ctx->fused_truncpr_max,
+                         ctx->fused_mul_max, ctx->fused_randbit_max, ctx->pair_decode_min};
+}
 
 // One batch decode.  Its forms (group, second_coeff, only_coeff, pair) are those of RecoverShape (recover_route.hpp); a form that
 // does not cover the call answers HBMPC_NOT_FUSED with nothing enqueued, and the caller runs the separate launches.
@@ -562,6 +567,42 @@ ShareErrorCode batch_recover_host(hbmpc_ctx* ctx, const size_t* sender_ids, size
     return ShareSuccess;
 }
 
+// hbmpc_[gl_]dev_recover_check_degree_strided: the decode of `groups` verifiers' G chunks each (group q's values q * group_stride
+// elements further on in every sender row) and the exact-degree test of what it decoded
+template <class T>
+ShareErrorCode recover_check_degree_dev(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const T* evals_dev, size_t row_stride, size_t G, size_t n,
+                                        size_t t, size_t groups, size_t group_stride, T* ws_dev, uint8_t* status_out_dev,
+                                        hbmpc_recover_summary* summary_dev, uint32_t* bad_dev, void* stream) {
+    if (!ctx) return InvalidInput;
+    if (!ws_dev || !bad_dev || groups == 0) return fail(ctx, InvalidInput, "null buffer or no group");
+    // a verifier that fires at 2t + 1 arrivals has no OEC round: the top coefficient alone decides the exact degree
+    const bool top_only = ctx->list_rows_in_kernel && S == 2 * t + 1 && ctx->direct_fail;
+    RecoverCall c{.sender_ids = sender_ids, .S = S, .evals = evals_dev, .row_stride = row_stride, .G = G, .n = n, .d = t, .t = t, .out = ws_dev,
+                  .status = status_out_dev, .summary = summary_dev, .stream = stream};
+    if (top_only) c.p0 = true, c.only_coeff = (int)t;
+    if (groups > 1) {  // several verifiers: one launch where the wave-per-chunk decode takes them, else one by one
+        if (top_only) {
+            RecoverCall all = c;
+            all.G = groups * G;
+            // groups that follow each other inside the sender rows (group_stride == G) are one plain call of groups * G chunks
+            if (group_stride != G) all.group = G, all.group_stride = group_stride;
+            const ShareErrorCode rc = batch_recover_dev(ctx, all);
+            if (rc == ShareSuccess) return check_top_coeff_any(ctx, ws_dev, status_out_dev, groups * G, t, bad_dev, stream, G);
+            if (rc != HBMPC_NOT_FUSED) return rc;
+        }
+        for (size_t q = 0; q < groups; ++q) {
+            const ShareErrorCode rc = recover_check_degree_dev(ctx, sender_ids, S, evals_dev + q * group_stride, row_stride, G, n, t, 1, 0, ws_dev,
+                                                               status_out_dev, summary_dev, bad_dev, stream);
+            if (rc != ShareSuccess) return rc;
+        }
+        return ShareSuccess;
+    }
+    const ShareErrorCode rc = batch_recover_dev(ctx, c);
+    if (rc != ShareSuccess) return rc;
+    if (top_only) return hbmpc_dev_check_top_coeff(ctx, ws_dev, status_out_dev, G, t, bad_dev, stream);
+    return hbmpc_dev_check_degree(ctx, ws_dev, status_out_dev, G, t + 1, t, bad_dev, stream);
+}
+
 }  // namespace
 
 #define TYPED_RECOVER(T, REQ, PFX)                                                                                        \
@@ -607,40 +648,8 @@ ShareErrorCode batch_recover_host(hbmpc_ctx* ctx, const size_t* sender_ids, size
         size_t t, size_t groups, size_t group_stride, T* ws_dev, uint8_t* status_out_dev,                                 \
         hbmpc_recover_summary* summary_dev, uint32_t* bad_dev, void* stream) {                                            \
         REQ(ctx);                                                                                                         \
-        if (ctx && (!ws_dev || !bad_dev || groups == 0)) return fail(ctx, InvalidInput, "null buffer or no group");       \
-        /* a verifier that fires at 2t + 1 arrivals has no OEC round: the top coefficient alone decides the exact degree */ \
-        const bool top_only = ctx->list_rows_in_kernel && S == 2 * t + 1 && ctx->direct_fail;                              \
-        if (groups > 1) { /* several verifiers: one launch where the wave-per-chunk decode takes them, else one by one */  \
-            if (top_only) {                                                                                               \
-                /* groups that follow each other inside the sender rows (group_stride == G) are one plain call of groups * G chunks */ \
-                const bool dense = group_stride == G;                                                                     \
-                const ShareErrorCode rc = batch_recover_dev(                                                              \
-                    ctx, {.sender_ids = sender_ids, .S = S, .evals = evals_dev, .row_stride = row_stride, .G = groups * G, .n = n, \
-                          .d = t, .t = t, .out = ws_dev, .status = status_out_dev, .summary = summary_dev, .p0 = true,     \
-                          .stream = stream, .only_coeff = (int)t, .group = dense ? 0 : G, .group_stride = dense ? 0 : group_stride}); \
-                if (rc == ShareSuccess) return check_top_coeff_any(ctx, ws_dev, status_out_dev, groups * G, t, bad_dev, stream, G); \
-                if (rc != HBMPC_NOT_FUSED) return rc;                                                                     \
-            }                                                                                                             \
-            for (size_t q = 0; q < groups; ++q) {                                                                         \
-                const ShareErrorCode rc = PFX##dev_recover_check_degree_strided(ctx, sender_ids, S, evals_dev + q * group_stride, \
-                                                                                row_stride, G, n, t, 1, 0, ws_dev, status_out_dev, \
-                                                                                summary_dev, bad_dev, stream);             \
-                if (rc != ShareSuccess) return rc;                                                                        \
-            }                                                                                                             \
-            return ShareSuccess;                                                                                          \
-        }                                                                                                                 \
-        if (top_only) {                                                                                                   \
-            ShareErrorCode rc = batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .evals = evals_dev, .row_stride = row_stride, \
-                                                        .G = G, .n = n, .d = t, .t = t, .out = ws_dev, .status = status_out_dev, \
-                                                        .summary = summary_dev, .p0 = true, .stream = stream, .only_coeff = (int)t}); \
-            if (rc != ShareSuccess) return rc;                                                                            \
-            return hbmpc_dev_check_top_coeff(ctx, ws_dev, status_out_dev, G, t, bad_dev, stream);                         \
-        }                                                                                                                 \
-        ShareErrorCode rc = batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .evals = evals_dev, .row_stride = row_stride, \
-                                                    .G = G, .n = n, .d = t, .t = t, .out = ws_dev, .status = status_out_dev,     \
-                                                    .summary = summary_dev, .stream = stream});                                 \
-        if (rc != ShareSuccess) return rc;                                                                                \
-        return hbmpc_dev_check_degree(ctx, ws_dev, status_out_dev, G, t + 1, t, bad_dev, stream);                         \
+        return recover_check_degree_dev(ctx, sender_ids, S, evals_dev, row_stride, G, n, t, groups, group_stride, ws_dev, \
+                                        status_out_dev, summary_dev, bad_dev, stream);                                    \
     }                                                                                                                     \
     extern "C" ShareErrorCode PFX##dev_batch_recover_slots(                                                               \
         hbmpc_ctx* ctx, const size_t* sender_ids, const size_t* row_slots, size_t S, const T* evals_dev, size_t row_stride, \

@@ -23,64 +23,49 @@ extern "C" ShareErrorCode hbmpc_fixed_point_reciprocal_scaled(const U256* denom,
     return ShareSuccess;
 }
 
-// The call is ONE launch for a small batch opened from exactly 2t + 1 senders (kernels_truncpr_wave.hpp), and otherwise
-// k_truncpr_front, hbmpc_dev_batch_recover_p0 and hbmpc_dev_truncpr_finalize_parties -- the same bytes in every output buffer.
+// The call is ONE launch, a wave per element (kernels_truncpr_wave.hpp), or k_truncpr_front, hbmpc_dev_batch_recover_p0 and
+// hbmpc_dev_truncpr_finalize_parties -- the same bytes in every output buffer.  Which: plan_protocol (protocol_route.hpp).
 extern "C" ShareErrorCode hbmpc_dev_truncpr_parties(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const U256* a, const U256* w_dev,
                                                     const U256* r_bits, const U256* r_int, size_t k, size_t m, size_t N, size_t n, size_t t,
                                                     U256* c_out, U256* r_dash_out, U256* open_sh_out, U256* c_open_out, U256* d_out,
                                                     uint8_t* status_out, hbmpc_recover_summary* summary_dev, void* stream) {
     if (!ctx) return InvalidInput;
     REQ_FR(ctx);
-    if (k == 0) return fail(ctx, InvalidInput, "k must be >= 1 (2^(k-1))");
-    if (m > 4096) return fail(ctx, InvalidInput, "m beyond the supported range");
-    if (m % 8 != 0 && m / 8 >= 32) return fail(ctx, InvalidInput, "m: bytes[m/8] out of bounds in the reference");
+    if (!truncpr_params_ok(ctx, TP_ALL, k, m)) return InvalidInput;
     if (!sender_ids || !a || !r_int || (m && !r_bits) || !r_dash_out || !open_sh_out || !c_open_out || !d_out) return fail(ctx, InvalidInput, "null buffer");
     if (w_dev && !c_out) return fail(ctx, InvalidInput, "a multiplier needs c_out for the products");
-    if (N == 0 || n == 0 || n > 255) return fail(ctx, InvalidInput, "N, n out of range");
+    if (!batch_in_range(ctx, N, n)) return InvalidInput;
     SortedSenders ss;  // before the first launch: a call that is refused has written nothing
     ShareErrorCode rc = validate_senders(ctx, sender_ids, S, N, n, t, t, &ss);
     if (rc != ShareSuccess) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = pick(ctx, stream);
     const int impl = ctx->impl;
-    const uint32_t* pow2;
-    rc = get_table(ctx, key("pow2", {m}, impl), [&] { return build_pow2(m, impl); }, &pow2);
+    const ProtocolPlan plan = plan_protocol(protocol_knobs(ctx), {ProtocolCall::TruncPr, N, n, t, S, 0});
+    TruncprConsts tc;  // 2^-m only for the one launch: the separate launches' last step fetches its own
+    rc = truncpr_consts(ctx, k, m, plan.one_launch, &tc);
     if (rc != ShareSuccess) return rc;
-    const HFr two = HFr::from_u64(2);
-    const HFr p2m = two.pow_u64(m), p2k = two.pow_u64(k - 1);
-    const ElemConsts cs = elem_consts(impl, &p2m, &p2k);
-    if (N <= ctx->fused_truncpr_max && S == 2 * t + 1 && impl == IMPL_U29 && !ctx->force_generic && ctx->direct_fail && n <= 64 && t <= 30) {
+    if (plan.one_launch) {
         TruncprWaveArgs ta;
         memset(&ta, 0, sizeof ta);
         ta.N = N, ta.parties = (int)n, ta.m = (int)m, ta.needed = (int)(2 * t + 1), ta.M = (int)(t + 1), ta.mask_bits = (int)(m > 256 ? 256 : m);
-        ta.w = (const uint32_t*)w_dev;
-        // the products of a table row are shared by up to four adjacent lanes (a DPP quad) while the rows still fit the wave
-        while (ta.lk < 2 && ((t + 1) << (ta.lk + 1)) <= 64 && ((size_t)2 << ta.lk) <= t + 1) ++ta.lk;
+        ta.w = (const uint32_t*)w_dev, ta.lk = plan.lk_wave;
         if (launch_truncpr_wave(ta, ctx->device, s, true)) {
             rc = fpmul_wave_table(ctx, ss, n, t, &ta.tab);  // its first t + 1 rows: the verify rows and the P(0) row
             if (rc != ShareSuccess) return rc;
-            const HFr inv = inv_pow2(ctx, m);
-            const ElemConsts ci = elem_consts(impl, &inv);
-            memcpy(ta.c0, cs.c0, sizeof ta.c0), memcpy(ta.c1, cs.c1, sizeof ta.c1), memcpy(ta.cinv, ci.c0, sizeof ta.cinv), memcpy(ta.r2, cs.r2, sizeof ta.r2);
-            ta.pow2 = pow2;
-            ta.a = (const uint32_t*)a, ta.r_bits = (const uint32_t*)r_bits, ta.r_int = (const uint32_t*)r_int;
+            memcpy(ta.c0, tc.cs.c0, sizeof ta.c0), memcpy(ta.c1, tc.cs.c1, sizeof ta.c1), memcpy(ta.cinv, tc.ci.c0, sizeof ta.cinv), memcpy(ta.r2, tc.cs.r2, sizeof ta.r2);
+            ta.a = (const uint32_t*)a, ta.r_bits = (const uint32_t*)r_bits, ta.r_int = (const uint32_t*)r_int, ta.pow2 = tc.pow2;
             ta.c = (uint32_t*)c_out, ta.r_dash = (uint32_t*)r_dash_out, ta.open_sh = (uint32_t*)open_sh_out;
             ta.out = (uint32_t*)d_out, ta.c_open = (uint32_t*)c_open_out, ta.status = status_out;
             for (size_t i = 0; i < S; ++i) ta.rows.set(i, (unsigned)ss.rows[i]);  // row s of the arrays is sender_ids[s]'s, as the decode call reads them
-            return with_decode_counters(ctx, s, 2048, [&](uint32_t* counters) -> ShareErrorCode {
-                ta.counters = counters;
-                ta.summary = summary_dev ? (uint32_t*)summary_dev : counters + 4;  // the scratch's local summary slot
-                launch_truncpr_wave(ta, ctx->device, s, false);
-                HIP_TRY(ctx, hipGetLastError());
-                return ShareSuccess;  // the kernel's last workgroup leaves the counters at zero
-            });
+            return enqueue_one_launch(ctx, s, &ta.counters, {{&ta.summary, summary_dev}}, [&] { launch_truncpr_wave(ta, ctx->device, s, false); });
         }
     }
     // a grid row per party at every size.  k_fpmul_middle's rule (one thread for all parties from 2^16 elements, so that the public
     // operand is converted once) loses here: a thread's n rounds of m + 2 dependent loads cost more than n - 1 conversions of w
     // save (profiles/fpdiv_bench.txt: 0.285 against 0.185 ms at 2^16, level at 2^18); the kernel itself serves any gridDim.y
     const unsigned grid_parties = (unsigned)n;
-    launch_truncpr_front(impl, as_words(a), as_words(w_dev), as_words(r_bits), as_words(r_int), (int)m, N, cs, pow2, as_words(c_out),
+    launch_truncpr_front(impl, as_words(a), as_words(w_dev), as_words(r_bits), as_words(r_int), (int)m, N, tc.cs, tc.pow2, as_words(c_out),
                          as_words(r_dash_out), as_words(open_sh_out), (unsigned)n, grid_parties, s);
     HIP_TRY(ctx, hipGetLastError());
     rc = hbmpc_dev_batch_recover_p0(ctx, sender_ids, S, open_sh_out, N, n, t, t, c_open_out, status_out, summary_dev, stream);

@@ -31,6 +31,7 @@
 #include "kernels_mfma_gl.hpp"
 #include "encode_route.hpp"
 #include "recover_route.hpp"
+#include "protocol_route.hpp"
 #include "tables_sqrt.hpp"
 #include "tables_riss.hpp"
 
@@ -145,6 +146,25 @@ struct DevBlockGuard {
         return q;
     }
 };
+// Bound the cache in a long-running node (every new sender set is a new table); ctx->mu is held.  Eviction is two-phase so
+// that a concurrent call which has looked a table up but not launched yet never sees it freed: tables
+// evicted now are only unlinked, and freed at the NEXT flush (>= 512 table builds later), after a device
+// synchronise for kernels still running on caller streams.  Tables a captured graph references stay.
+static void flush_tables_if_full(hbmpc_ctx* ctx) {
+    if (ctx->tables.size() < 512) return;
+    ++ctx->evictions;
+    (void)hipDeviceSynchronize();
+    for (uint32_t* q : ctx->retired_tables) (void)hipFree(q);
+    ctx->retired_tables.clear();
+    for (auto t = ctx->tables.begin(); t != ctx->tables.end();) {
+        if (t->second.pinned) {
+            ++t;
+            continue;
+        }
+        ctx->retired_tables.push_back(t->second.p);
+        t = ctx->tables.erase(t);
+    }
+}
 template <class Build>
 static ShareErrorCode get_table(hbmpc_ctx* ctx, const std::string& key, Build build, const uint32_t** out,
                                 std::array<size_t, 5>* aux = nullptr) {
@@ -157,24 +177,7 @@ static ShareErrorCode get_table(hbmpc_ctx* ctx, const std::string& key, Build bu
         return ShareSuccess;
     }
     if (g_capturing) return fail(ctx, HBMPC_NO_DEVICE, "a table would have to be built during graph capture: run the call sequence once eagerly first");
-    if (ctx->tables.size() >= 512) {
-        // Bound the cache in a long-running node (every new sender set is a new table).  Eviction is two-phase so
-        // that a concurrent call which has looked a table up but not launched yet never sees it freed: tables
-        // evicted now are only unlinked, and freed at the NEXT flush (>= 512 table builds later), after a device
-        // synchronise for kernels still running on caller streams.  Tables a captured graph references stay.
-        ++ctx->evictions;
-        (void)hipDeviceSynchronize();
-        for (uint32_t* q : ctx->retired_tables) (void)hipFree(q);
-        ctx->retired_tables.clear();
-        for (auto t = ctx->tables.begin(); t != ctx->tables.end();) {
-            if (t->second.pinned) {
-                ++t;
-                continue;
-            }
-            ctx->retired_tables.push_back(t->second.p);
-            t = ctx->tables.erase(t);
-        }
-    }
+    flush_tables_if_full(ctx);
     std::vector<uint32_t> host = build();
     if (host.empty()) host.push_back(0);
     DevBlockGuard blk;
@@ -201,20 +204,7 @@ static ShareErrorCode get_table_expanded(hbmpc_ctx* ctx, const std::string& key,
         return ShareSuccess;
     }
     if (g_capturing) return fail(ctx, HBMPC_NO_DEVICE, "a table would have to be built during graph capture: run the call sequence once eagerly first");
-    if (ctx->tables.size() >= 512) {  // same two-phase flush as get_table
-        ++ctx->evictions;
-        (void)hipDeviceSynchronize();
-        for (uint32_t* q : ctx->retired_tables) (void)hipFree(q);
-        ctx->retired_tables.clear();
-        for (auto t = ctx->tables.begin(); t != ctx->tables.end();) {
-            if (t->second.pinned) {
-                ++t;
-                continue;
-            }
-            ctx->retired_tables.push_back(t->second.p);
-            t = ctx->tables.erase(t);
-        }
-    }
+    flush_tables_if_full(ctx);
     // (ctx->mu is held across the build and the drain of the context's own stream: a second thread that wants the SAME new table
     // must find it finished, and builds are rare -- one per new sender set -- and short, two launches of a few microseconds)
     std::vector<uint32_t> seed = build_seed();
@@ -332,6 +322,37 @@ static HFr inv_pow2(hbmpc_ctx* ctx, size_t m) {
     ctx->inv_pow2.emplace(m, v);
     return v;
 }
+// TruncPr's constants (truncpr.rs:277-297, 216-220): the table of 2^i, cs.c0 = 2^m, cs.c1 = 2^(k-1) in plain limbs and, for the
+// one-launch kernels (the separate launches' last step fetches its own), ci.c0 = 2^-m
+struct TruncprConsts {
+    const uint32_t* pow2;
+    ElemConsts cs, ci;
+};
+static ShareErrorCode truncpr_consts(hbmpc_ctx* ctx, size_t k, size_t m, bool inv, TruncprConsts* out) {
+    const int impl = ctx->impl;
+    const ShareErrorCode rc = get_table(ctx, key("pow2", {m}, impl), [&] { return build_pow2(m, impl); }, &out->pow2);
+    if (rc != ShareSuccess) return rc;
+    const HFr two = HFr::from_u64(2);
+    const HFr p2m = two.pow_u64(m), p2k = two.pow_u64(k - 1);
+    out->cs = elem_consts(impl, &p2m, &p2k);
+    if (inv) {
+        const HFr i2m = inv_pow2(ctx, m);
+        out->ci = elem_consts(impl, &i2m);
+    }
+    return ShareSuccess;
+}
+// TruncPr's parameter checks, each asked for by its bit.  False: the message is set and the call answers InvalidInput.
+enum { TP_K = 1, TP_M = 2, TP_BYTES = 4, TP_ALL = 7 };
+static bool truncpr_params_ok(hbmpc_ctx* ctx, int which, size_t k, size_t m) {
+    if ((which & TP_K) && k == 0) return fail(ctx, InvalidInput, "k must be >= 1 (2^(k-1))"), false;
+    if ((which & TP_M) && m > 4096) return fail(ctx, InvalidInput, "m beyond the supported range"), false;
+    // fpmul/mod.rs:381-406 indexes bytes[m/8] when m % 8 != 0: out of bounds (a panic) from m = 257 on
+    if ((which & TP_BYTES) && m % 8 != 0 && m / 8 >= 32) return fail(ctx, InvalidInput, "m: bytes[m/8] out of bounds in the reference"), false;
+    return true;
+}
+static bool batch_in_range(hbmpc_ctx* ctx, size_t N, size_t n) {  // N elements of each of n <= 255 parties; false as above
+    return (N != 0 && n != 0 && n <= 255) || (fail(ctx, InvalidInput, "N, n out of range"), false);
+}
 // ---- context -----------------------------------------------------------------------------------
 extern "C" const char* hbmpc_version(void) { return "hbmpc-hip 0.1 (gfx950)"; }
 
@@ -412,26 +433,20 @@ extern "C" ShareErrorCode hbmpc_set_matrix_cores(hbmpc_ctx* ctx, int on, size_t 
     }
     return ShareSuccess;
 }
-extern "C" ShareErrorCode hbmpc_set_fused_fpmul(hbmpc_ctx* ctx, size_t max_elements) {
-    if (!ctx) return InvalidInput;
-    ctx->fused_fpmul_max = max_elements;
-    return ShareSuccess;
-}
-extern "C" ShareErrorCode hbmpc_set_fused_truncpr(hbmpc_ctx* ctx, size_t max_elements) {
-    if (!ctx) return InvalidInput;
-    ctx->fused_truncpr_max = max_elements;
-    return ShareSuccess;
-}
-extern "C" ShareErrorCode hbmpc_set_fused_triplegen(hbmpc_ctx* ctx, size_t max_chunks) {
-    if (!ctx) return InvalidInput;
-    ctx->fused_triplegen_max = max_chunks;
-    return ShareSuccess;
-}
-extern "C" ShareErrorCode hbmpc_set_fpmul_pair_decode(hbmpc_ctx* ctx, size_t min_elements) {
-    if (!ctx) return InvalidInput;
-    ctx->pair_decode_min = min_elements;
-    return ShareSuccess;
-}
+// the thresholds of the protocol calls' rule (protocol_route.hpp)
+#define KNOB_SETTER(NAME, FIELD)                                   \
+    extern "C" ShareErrorCode NAME(hbmpc_ctx* ctx, size_t value) { \
+        if (!ctx) return InvalidInput;                             \
+        ctx->FIELD = value;                                        \
+        return ShareSuccess;                                       \
+    }
+KNOB_SETTER(hbmpc_set_fused_fpmul, fused_fpmul_max)
+KNOB_SETTER(hbmpc_set_fused_truncpr, fused_truncpr_max)
+KNOB_SETTER(hbmpc_set_fused_triplegen, fused_triplegen_max)
+KNOB_SETTER(hbmpc_set_fused_mul, fused_mul_max)
+KNOB_SETTER(hbmpc_set_fused_randbit, fused_randbit_max)
+KNOB_SETTER(hbmpc_set_fpmul_pair_decode, pair_decode_min)
+#undef KNOB_SETTER
 extern "C" ShareErrorCode hbmpc_set_gather_row_copies(hbmpc_ctx* ctx, int on) {  // either field
     if (!ctx) return InvalidInput;
     ctx->gather_row_copies = on != 0;
@@ -1547,7 +1562,7 @@ static ShareErrorCode truncpr_rdash_impl(hbmpc_ctx* ctx, const U256* r_bits, siz
     REQ_FR(ctx);
     ELEM_PROLOGUE
     CHECK_PARTIES(parties);
-    if (m > 4096) return fail(ctx, InvalidInput, "m beyond the supported range");
+    if (!truncpr_params_ok(ctx, TP_M, 0, m)) return InvalidInput;
     const uint32_t* pow2;
     const int impl = ctx->impl;
     ShareErrorCode rc = get_table(ctx, key("pow2", {m}, impl), [&] { return build_pow2(m, impl); }, &pow2);
@@ -1568,7 +1583,7 @@ extern "C" ShareErrorCode hbmpc_dev_truncpr_open_share(hbmpc_ctx* ctx, const U25
                                                        const U256* r_int, size_t k, size_t m, size_t N, U256* open_out,
                                                        void* stream) {
     REQ_FR(ctx);
-    if (ctx && k == 0) return fail(ctx, InvalidInput, "k must be >= 1 (2^(k-1))");
+    if (ctx && !truncpr_params_ok(ctx, TP_K, k, m)) return InvalidInput;
     ELEM_PROLOGUE
     const HFr two = HFr::from_u64(2);
     const HFr p2m = two.pow_u64(m), p2k = two.pow_u64(k - 1);
@@ -1581,20 +1596,16 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_middle(hbmpc_ctx* ctx, const U256* c, 
                                                  const U256* e, const U256* r_bits, const U256* r_int, size_t k, size_t m, size_t N,
                                                  size_t parties, U256* z_out, U256* r_dash_out, U256* open_out, void* stream) {
     REQ_FR(ctx);
-    if (ctx && k == 0) return fail(ctx, InvalidInput, "k must be >= 1 (2^(k-1))");
+    if (ctx && !truncpr_params_ok(ctx, TP_K, k, m)) return InvalidInput;
     ELEM_PROLOGUE
     CHECK_PARTIES(parties);
-    if (m > 4096) return fail(ctx, InvalidInput, "m beyond the supported range");
+    if (!truncpr_params_ok(ctx, TP_M, k, m)) return InvalidInput;
     if (!c || !x || !y || !d || !e || !r_int || !z_out || !r_dash_out || !open_out || (m && !r_bits)) return fail(ctx, InvalidInput, "null buffer");
-    const uint32_t* pow2;
-    const int impl = ctx->impl;
-    ShareErrorCode rc = get_table(ctx, key("pow2", {m}, impl), [&] { return build_pow2(m, impl); }, &pow2);
+    TruncprConsts tc;
+    const ShareErrorCode rc = truncpr_consts(ctx, k, m, false, &tc);
     if (rc != ShareSuccess) return rc;
-    const HFr two = HFr::from_u64(2);
-    const HFr p2m = two.pow_u64(m), p2k = two.pow_u64(k - 1);
-    const ElemConsts cs = elem_consts(impl, &p2m, &p2k);
     const unsigned grid_parties = N >= ((size_t)1 << 16) ? 1 : (unsigned)parties;  // k_beaver_finalize's rule
-    launch_fpmul_middle(impl, as_words(c), as_words(x), as_words(y), as_words(d), as_words(e), as_words(r_bits), as_words(r_int), (int)m, N, cs, pow2,
+    launch_fpmul_middle(ctx->impl, as_words(c), as_words(x), as_words(y), as_words(d), as_words(e), as_words(r_bits), as_words(r_int), (int)m, N, tc.cs, tc.pow2,
                         as_words(z_out), as_words(r_dash_out), as_words(open_out), (unsigned)parties, grid_parties, s);
     HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
@@ -1602,8 +1613,7 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_middle(hbmpc_ctx* ctx, const U256* c, 
 static ShareErrorCode truncpr_finalize_impl(hbmpc_ctx* ctx, const U256* a, const U256* r_dash, const U256* c_open, size_t m,
                                             size_t N, size_t parties, U256* d_out, void* stream) {
     REQ_FR(ctx);
-    // fpmul/mod.rs:381-406 indexes bytes[m/8] when m % 8 != 0: out of bounds (a panic) from m = 257 on
-    if (ctx && m % 8 != 0 && m / 8 >= 32) return fail(ctx, InvalidInput, "m: bytes[m/8] out of bounds in the reference");
+    if (ctx && !truncpr_params_ok(ctx, TP_BYTES, 0, m)) return InvalidInput;
     ELEM_PROLOGUE
     CHECK_PARTIES(parties);
     const HFr inv = inv_pow2(ctx, m);
@@ -2084,25 +2094,66 @@ extern "C" ShareErrorCode hbmpc_dev_check_double_share_c0(hbmpc_ctx* ctx, const 
 #include "capi_recover.inc"
 #include "capi_riss.inc"
 
+// ---- whole protocol steps for all parties on this device ------------------------------------------------------------------------
+// Which form each call takes is decided in one place, plan_protocol (protocol_route.hpp); what follows is shared by their executors.
+static std::vector<size_t> first_ids(size_t count) {  // senders 0 .. count - 1
+    std::vector<size_t> ids(count);
+    for (size_t i = 0; i < count; ++i) ids[i] = i;
+    return ids;
+}
+// The enqueue of a one-launch protocol kernel: the decode's counters at the start of the stream's scratch go to *counters, every
+// summary (kernel argument, caller's buffer) the caller did not ask for to the scratch's local summary slot, then launch() -- void,
+// or a ShareErrorCode -- and its error.  The kernel's last workgroup leaves the counters at zero.
+template <class Launch>
+static ShareErrorCode enqueue_one_launch(hbmpc_ctx* ctx, hipStream_t s, uint32_t** counters,
+                                         std::initializer_list<std::pair<uint32_t**, hbmpc_recover_summary*>> summaries, Launch launch) {
+    return with_decode_counters(ctx, s, 2048, [&](uint32_t* c) -> ShareErrorCode {
+        *counters = c;
+        for (const auto& sm : summaries) *sm.first = sm.second ? (uint32_t*)sm.second : c + 4;
+        if constexpr (std::is_void<decltype(launch())>::value) launch();
+        else if (const ShareErrorCode rc = launch(); rc != ShareSuccess) return rc;
+        HIP_TRY(ctx, hipGetLastError());
+        return ShareSuccess;
+    });
+}
+// The shares Multiply opens (multiplication.rs:417-426) and reconstruct_rbc's recover_secret of a - x and of b - y (:102-139): ONE
+// P(0) decode over the 2 N values of a sender row, into de_out [2][N].
+// pair_first (large batches): the shares are formed as the matrix-core decode loads them (kernels_mfma.hpp, k_mfma_rows<.., SUB>) --
+// 4 (2t + 1) loads per element instead of a launch that writes all n parties' two shares and a decode that reads 2t + 1 of them
+// back (config 5: 0.14 + 0.065 ms -> 0.11).  Otherwise, and when the decode declines that form: the shares go to de_sh_ws
+// [party][2][N] and the decode reads row s as sender_ids[s]'s or, with slots, every sender's row in place at its party id.
+static ShareErrorCode open_beaver_pair(hbmpc_ctx* ctx, bool pair_first, bool slots, const size_t* sender_ids, size_t S, const void* a, const void* b,
+                                       const void* x, const void* y, size_t N, size_t n, size_t t, void* de_sh_ws, void* de_out, uint8_t* status_out,
+                                       hbmpc_recover_summary* summary_dev, void* stream) {
+    RecoverCall c{.sender_ids = sender_ids, .S = S, .G = 2 * N, .n = n, .d = t, .t = t, .out = de_out, .status = status_out, .summary = summary_dev,
+                  .p0 = true, .stream = stream};
+    const PairInput pi = {as_words(a), as_words(b), as_words(x), as_words(y), N};
+    if (pair_first) {
+        c.pair = &pi;
+        const ShareErrorCode rc = batch_recover_dev(ctx, c);
+        if (rc != HBMPC_NOT_FUSED) return rc;
+        c.pair = nullptr;
+    }
+    const ShareErrorCode rc = beaver_open_pair_any(ctx, a, b, x, y, N, n, de_sh_ws, stream);
+    if (rc != ShareSuccess) return rc;
+    c.evals = de_sh_ws, c.slots = slots ? sender_ids : nullptr;
+    return batch_recover_dev(ctx, c);
+}
+
 // ---- TripleGenNode for all parties on this device (triple_gen/triple_generation.rs:304-364) --------------------------------------
 // T: U256 (H = HFr) or uint64_t (H = HGl)
 template <class H, class T>
 static ShareErrorCode triplegen_parties_any(hbmpc_ctx* ctx, const T* a, const T* b, const T* r2t, const T* rt, size_t N, size_t n, size_t t, T* y_ws,
                                             T* z_ws, T* opened_out, T* c_out, uint8_t* status_out, hbmpc_recover_summary* summary_first_dev,
                                             hbmpc_recover_summary* summary_dev, void* stream) {
-    constexpr bool gold = std::is_same<T, uint64_t>::value;
+    if (!ctx) return InvalidInput;
     if (!a || !b || !r2t || !rt || !y_ws || !z_ws || !opened_out || !c_out) return fail(ctx, InvalidInput, "null buffer");
     const size_t M = 2 * t + 1, d = 2 * t;
     if (N == 0 || n == 0 || n > 255 || N % M != 0) return fail(ctx, InvalidInput, "N must be a positive multiple of 2t + 1; n in 1 .. 255");
     if (n < 3 * t + 1) return fail(ctx, InvalidInput, "n must be >= 3t + 1 for Byzantine fault tolerance");
     const size_t G = N / M;
-    std::vector<size_t> ids(n);
-    for (size_t i = 0; i < n; ++i) ids[i] = i;
-    // Small batches: one launch, a workgroup per chunk (kernels_triplegen_wg.hpp).  n = 3t + 1 <= 16: every recipient decodes from
-    // exactly d + t + 1 senders (no OEC round), and the (party, recipient) pairs fit the workgroup.
-    // (over Goldilocks the four launches are flat at ~28 us and overtake at ~600 chunks: half the threshold)
-    if (G <= (gold ? ctx->fused_triplegen_max / 2 : ctx->fused_triplegen_max) && n == 3 * t + 1 && n <= 16 && (gold || ctx->impl == IMPL_U29) &&
-        !ctx->force_generic && ctx->direct_fail) {
+    const std::vector<size_t> ids = first_ids(n);
+    if (plan_protocol(protocol_knobs(ctx), {ProtocolCall::TripleGen, N, n, t, 0, 0}).one_launch) {  // a workgroup per chunk (kernels_triplegen_wg.hpp)
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         hipStream_t s = pick(ctx, stream);
         const int impl = ctx->impl;
@@ -2117,37 +2168,21 @@ static ShareErrorCode triplegen_parties_any(hbmpc_ctx* ctx, const T* a, const T*
         ta.a = (const uint32_t*)a, ta.b = (const uint32_t*)b, ta.r2t = (const uint32_t*)r2t, ta.rt = (const uint32_t*)rt;
         ta.Y = (uint32_t*)y_ws, ta.Z = (uint32_t*)z_ws, ta.opened = (uint32_t*)opened_out, ta.c = (uint32_t*)c_out, ta.status = status_out;
         ta.G = G, ta.N = N, ta.n = (int)n, ta.t = (int)t;
-        return with_decode_counters(ctx, s, 2048, [&](uint32_t* counters) -> ShareErrorCode {
-            ta.counters = counters;
-            ta.summary_first = summary_first_dev ? (uint32_t*)summary_first_dev : counters + 4;
-            ta.summary = summary_dev ? (uint32_t*)summary_dev : counters + 4;
-            launch_triplegen_wg(impl, ta, s);
-            HIP_TRY(ctx, hipGetLastError());
-            return ShareSuccess;  // the kernel's last workgroup leaves the counters at zero
-        });
+        return enqueue_one_launch(ctx, s, &ta.counters, {{&ta.summary_first, summary_first_dev}, {&ta.summary, summary_dev}}, [&] { launch_triplegen_wg(impl, ta, s); });
     }
     // [ab - r]_2t Vandermonde-encoded in chunks of 2t + 1 for every recipient (batch_recon.rs:157-165), all parties in one launch;
     // EvalBatch arm for ALL recipients in one call: the row of sender p for "chunk" j G + g is y_ws + p (n G) + (j G + g);
     // RevealBatch arm: everyone interpolates the 2t + 1 opened values per chunk from the n broadcast values;
     // [c]_t = rt_i + opened (triple_generation.rs:196-208)
-    ShareErrorCode rc;
-    if constexpr (gold) {
-        rc = hbmpc_gl_dev_triple_encode_parties(ctx, a, b, r2t, G, n, d, n, c_out, y_ws, stream);
-        if (rc != ShareSuccess) return rc;
-        rc = hbmpc_gl_dev_batch_recover_strided(ctx, ids.data(), n, y_ws, n * G, n * G, n, d, t, 1, z_ws, nullptr, status_out, summary_first_dev, stream);
-        if (rc != ShareSuccess) return rc;
-        rc = hbmpc_gl_dev_batch_recover(ctx, ids.data(), n, z_ws, G, n, d, t, opened_out, nullptr, status_out, summary_dev, stream);
-        if (rc != ShareSuccess) return rc;
-        return hbmpc_gl_dev_triple_finalize_parties(ctx, rt, opened_out, N, n, c_out, stream);
-    } else {
-        rc = hbmpc_dev_triple_encode_parties(ctx, a, b, r2t, G, n, d, n, c_out, y_ws, stream);
-        if (rc != ShareSuccess) return rc;
-        rc = hbmpc_dev_batch_recover_strided(ctx, ids.data(), n, y_ws, n * G, n * G, n, d, t, 1, z_ws, nullptr, status_out, summary_first_dev, stream);
-        if (rc != ShareSuccess) return rc;
-        rc = hbmpc_dev_batch_recover(ctx, ids.data(), n, z_ws, G, n, d, t, opened_out, nullptr, status_out, summary_dev, stream);
-        if (rc != ShareSuccess) return rc;
-        return hbmpc_dev_triple_finalize_parties(ctx, rt, opened_out, N, n, c_out, stream);
-    }
+    ShareErrorCode rc = triple_encode_any(ctx, a, b, r2t, G, n, d, n, c_out, y_ws, stream);
+    if (rc != ShareSuccess) return rc;
+    rc = batch_recover_dev(ctx, {.sender_ids = ids.data(), .S = n, .evals = y_ws, .row_stride = n * G, .G = n * G, .n = n, .d = d, .t = t, .out = z_ws,
+                                 .status = status_out, .summary = summary_first_dev, .p0 = true, .stream = stream});
+    if (rc != ShareSuccess) return rc;
+    rc = batch_recover_dev(ctx, {.sender_ids = ids.data(), .S = n, .evals = z_ws, .G = G, .n = n, .d = d, .t = t, .out = opened_out, .status = status_out,
+                                 .summary = summary_dev, .stream = stream});
+    if (rc != ShareSuccess) return rc;
+    return triple_finalize_any(ctx, rt, opened_out, N, c_out, stream, n);
 }
 extern "C" ShareErrorCode hbmpc_dev_triplegen_parties(hbmpc_ctx* ctx, const U256* a, const U256* b, const U256* r2t, const U256* rt, size_t N,
                                                       size_t n, size_t t, U256* y_ws, U256* z_ws, U256* opened_out, U256* c_out, uint8_t* status_out,
@@ -2179,75 +2214,47 @@ static ShareErrorCode fpmul_wave_table(hbmpc_ctx* ctx, const SortedSenders& ss, 
         return w;
     }, out);
 }
+// The call is ONE launch, a wave per element (kernels_fpmul_wave.hpp), or the five separate launches below -- the same bytes in
+// every output buffer.
 extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const U256* a, const U256* b, const U256* c,
                                                   const U256* x, const U256* y, const U256* r_bits, const U256* r_int, size_t k, size_t m, size_t N,
                                                   size_t n, size_t t, U256* de_sh_ws, U256* de_out, U256* z_out, U256* r_dash_out,
                                                   U256* open_sh_out, U256* c_open_out, U256* d_out, uint8_t* status_out,
                                                   hbmpc_recover_summary* summary_first_dev, hbmpc_recover_summary* summary_dev, void* stream) {
+    if (!ctx) return InvalidInput;
     REQ_FR(ctx);
-    if (k == 0) return fail(ctx, InvalidInput, "k must be >= 1 (2^(k-1))");
-    if (m > 4096) return fail(ctx, InvalidInput, "m beyond the supported range");
-    if (m % 8 != 0 && m / 8 >= 32) return fail(ctx, InvalidInput, "m: bytes[m/8] out of bounds in the reference");
+    if (!truncpr_params_ok(ctx, TP_ALL, k, m)) return InvalidInput;
     if (!a || !b || !c || !x || !y || !r_int || (m && !r_bits) || !de_sh_ws || !de_out || !z_out || !r_dash_out || !open_sh_out || !c_open_out || !d_out)
         return fail(ctx, InvalidInput, "null buffer");
-    if (N == 0 || n == 0 || n > 255) return fail(ctx, InvalidInput, "N, n out of range");
-    // Small batches: the whole multiplication is one launch, a wave per element (kernels_fpmul_wave.hpp).  Larger ones, calls
-    // with OEC rounds available (S > 2t + 1) and the other field implementations run the five separate launches below -- the
-    // same bytes in every output buffer.
-    if (N <= ctx->fused_fpmul_max && S == 2 * t + 1 && ctx->impl == IMPL_U29 && !ctx->force_generic && ctx->direct_fail && n <= 64 && t <= 30 &&
-        (4 + m) * n <= 4096) {
+    if (!batch_in_range(ctx, N, n)) return InvalidInput;
+    const ProtocolPlan plan = plan_protocol(protocol_knobs(ctx), {ProtocolCall::FpMul, N, n, t, S, m});
+    if (plan.one_launch) {
         SortedSenders ss;
         ShareErrorCode rc = validate_senders(ctx, sender_ids, S, N, n, t, t, &ss);
         if (rc != ShareSuccess) return rc;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         hipStream_t s = pick(ctx, stream);
-        const int impl = ctx->impl;
         FpmulWaveArgs fa;
         memset(&fa, 0, sizeof fa);
         fa.N = N, fa.parties = (int)n, fa.m = (int)m, fa.needed = (int)(2 * t + 1), fa.M = (int)(t + 1), fa.mask_bits = (int)(m > 256 ? 256 : m);
-        // the products of a table row are shared by up to four adjacent lanes (a DPP quad) while the rows still fit the wave
-        while (fa.lk1 < 2 && ((t + 2) << (fa.lk1 + 1)) <= 32 && ((size_t)2 << fa.lk1) <= t + 1) ++fa.lk1;
-        while (fa.lk3 < 2 && ((t + 1) << (fa.lk3 + 1)) <= 64 && ((size_t)2 << fa.lk3) <= t + 1) ++fa.lk3;
+        fa.lk1 = plan.lk_row, fa.lk3 = plan.lk_wave;
         if (launch_fpmul_wave(fa, ctx->device, s, true)) {
             rc = fpmul_wave_table(ctx, ss, n, t, &fa.tab);
             if (rc != ShareSuccess) return rc;
-            rc = get_table(ctx, key("pow2", {m}, impl), [&] { return build_pow2(m, impl); }, &fa.pow2);
+            TruncprConsts tc;
+            rc = truncpr_consts(ctx, k, m, true, &tc);
             if (rc != ShareSuccess) return rc;
-            const HFr two = HFr::from_u64(2);
-            const HFr p2m = two.pow_u64(m), p2k = two.pow_u64(k - 1), inv = inv_pow2(ctx, m);
-            const ElemConsts cs = elem_consts(impl, &p2m, &p2k), ci = elem_consts(impl, &inv);
-            memcpy(fa.c0, cs.c0, sizeof fa.c0), memcpy(fa.c1, cs.c1, sizeof fa.c1), memcpy(fa.cinv, ci.c0, sizeof fa.cinv);
+            memcpy(fa.c0, tc.cs.c0, sizeof fa.c0), memcpy(fa.c1, tc.cs.c1, sizeof fa.c1), memcpy(fa.cinv, tc.ci.c0, sizeof fa.cinv);
             fa.ta = (const uint32_t*)a, fa.tb = (const uint32_t*)b, fa.tc = (const uint32_t*)c, fa.x = (const uint32_t*)x, fa.y = (const uint32_t*)y;
-            fa.r_bits = (const uint32_t*)r_bits, fa.r_int = (const uint32_t*)r_int;
+            fa.r_bits = (const uint32_t*)r_bits, fa.r_int = (const uint32_t*)r_int, fa.pow2 = tc.pow2;
             fa.de_out = (uint32_t*)de_out, fa.z = (uint32_t*)z_out, fa.r_dash = (uint32_t*)r_dash_out, fa.open_sh = (uint32_t*)open_sh_out;
             fa.out = (uint32_t*)d_out, fa.c_open = (uint32_t*)c_open_out, fa.status = status_out;
             for (size_t i = 0; i < S; ++i) fa.rows.set(i, (unsigned)ss.ids[i]);  // the per-party arrays are indexed by party id
-            return with_decode_counters(ctx, s, 2048, [&](uint32_t* counters) -> ShareErrorCode {
-                fa.counters = counters;
-                fa.summary_first = summary_first_dev ? (uint32_t*)summary_first_dev : counters + 4;  // the scratch's local summary slot
-                fa.summary = summary_dev ? (uint32_t*)summary_dev : counters + 4;
-                launch_fpmul_wave(fa, ctx->device, s, false);
-                HIP_TRY(ctx, hipGetLastError());
-                return ShareSuccess;  // the kernel's last workgroup leaves the counters at zero
-            });
+            return enqueue_one_launch(ctx, s, &fa.counters, {{&fa.summary_first, summary_first_dev}, {&fa.summary, summary_dev}},
+                                      [&] { launch_fpmul_wave(fa, ctx->device, s, false); });
         }
     }
-    // the shares Multiply opens (multiplication.rs:417-426) and reconstruct_rbc's recover_secret of a - x and of b - y (:102-139):
-    // ONE interpolation over the 2 N values of a sender row
-    // Large batches: the shares are formed as the matrix-core decode loads them (kernels_mfma.hpp, k_mfma_rows<.., SUB>) -- 4 (2t + 1)
-    // loads per element instead of a launch that writes all n parties' two shares and a decode that reads 2t + 1 of them back
-    // (config 5: 0.14 + 0.065 ms -> 0.11; ahead from ~8 000 elements, tools/sweep_fused_fpmul.py).
-    ShareErrorCode rc = HBMPC_NOT_FUSED;
-    if (N >= ctx->pair_decode_min) {
-        PairInput pi = {(const uint32_t*)a, (const uint32_t*)b, (const uint32_t*)x, (const uint32_t*)y, N};
-        rc = batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .G = 2 * N, .n = n, .d = t, .t = t, .out = de_out, .status = status_out,
-                                     .summary = summary_first_dev, .p0 = true, .stream = stream, .pair = &pi});
-    }
-    if (rc == HBMPC_NOT_FUSED) {
-        rc = hbmpc_dev_beaver_open_shares_paired(ctx, a, b, x, y, N, n, de_sh_ws, stream);
-        if (rc != ShareSuccess) return rc;
-        rc = hbmpc_dev_batch_recover_p0(ctx, sender_ids, S, de_sh_ws, 2 * N, n, t, t, de_out, status_out, summary_first_dev, stream);
-    }
+    ShareErrorCode rc = open_beaver_pair(ctx, plan.pair_first, false, sender_ids, S, a, b, x, y, N, n, t, de_sh_ws, de_out, status_out, summary_first_dev, stream);
     if (rc != ShareSuccess) return rc;
     // finalize_mul (:57-100), r' (truncpr.rs:277-283), the share TruncPr opens (:294-297), its open (truncpr.rs:215), the last step (:216-220)
     rc = hbmpc_dev_fpmul_middle(ctx, c, x, y, de_out, de_out + N, r_bits, r_int, k, m, N, n, z_out, r_dash_out, open_sh_out, stream);

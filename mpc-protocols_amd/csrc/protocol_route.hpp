@@ -1,0 +1,67 @@
+// protocol_route.hpp -- which form a "whole protocol step for all parties" call takes: ONE place for the rule (plain C++, no HIP).
+//
+// hbmpc_[gl_]dev_triplegen_parties, hbmpc_dev_fpmul_parties, hbmpc_dev_truncpr_parties, hbmpc_[gl_]dev_mul_parties and
+// hbmpc_[gl_]dev_randbit_parties each ask plan_protocol once; either form writes the same bytes to every output buffer.
+// Two declines stay with the executor because they depend on a launcher or on the decode, not on the call's shape:
+//   - the launchers' dry run (launch_*_wave(.., true): the LDS size and the LDS attribute): the call then runs its separate launches;
+//   - the HBMPC_NOT_FUSED answer of batch_recover_dev to the pair form: the open then writes the shares and decodes them.
+#pragma once
+#include <stddef.h>
+
+#include "field_dispatch.hpp"
+
+namespace hbmpc {
+
+// the hbmpc_ctx fields the rule reads
+struct ProtocolKnobs {
+    int impl;
+    bool force_generic, direct_fail;
+    size_t fused_triplegen_max, fused_fpmul_max, fused_truncpr_max, fused_mul_max, fused_randbit_max;  // chunks, 3 x elements, chunks
+    size_t pair_decode_min;
+};
+enum class ProtocolCall { TripleGen, FpMul, TruncPr, Mul, RandBit };
+// the call: N elements per party, n parties, t faults, S senders (FPMul, TruncPr, Mul), m truncated bits (FPMul)
+struct ProtocolShape {
+    ProtocolCall call;
+    size_t N, n, t, S, m;
+};
+struct ProtocolPlan {
+    bool one_launch;  // a wave per element (FPMul, TruncPr, Mul) or a workgroup per chunk (TripleGen, RandBit) instead of the separate launches
+    // the wave kernels: 1 << lk adjacent lanes (a DPP quad at most) share the products of a table row
+    int lk_row;       // FPMul's lk1, Mul's lk: while the t + 2 rows fit half a wave
+    int lk_wave;      // FPMul's lk3, TruncPr's lk: while the t + 1 rows fit the wave
+    bool pair_first;  // FPMul, Mul: the separate launches offer the open of a - x and b - y to the decode's pair form first
+};
+
+inline int lane_share(size_t rows, size_t lanes, size_t t) {
+    int lk = 0;
+    while (lk < 2 && (rows << (lk + 1)) <= lanes && ((size_t)2 << lk) <= t + 1) ++lk;
+    return lk;
+}
+
+inline ProtocolPlan plan_protocol(const ProtocolKnobs& k, const ProtocolShape& s) {
+    const bool gold = k.impl == IMPL_GOLD, fpmul = s.call == ProtocolCall::FpMul, mul = s.call == ProtocolCall::Mul;
+    // one launch has no OEC round and writes a failed chunk itself, as the one-launch decodes do (recover_route.hpp)
+    const bool any = !k.force_generic && k.direct_fail;
+    // the wave-per-element kernels: Fr in 29-bit limbs, exactly 2t + 1 senders, a decode's rows fit the wave
+    const bool wave = any && k.impl == IMPL_U29 && s.S == 2 * s.t + 1 && s.n <= 64 && s.t <= 30;
+    bool one = false;
+    switch (s.call) {
+    case ProtocolCall::TripleGen:
+        // a chunk is 2t + 1 triples.  n = 3t + 1 <= 16: every recipient decodes from exactly d + t + 1 senders, and the (party, recipient)
+        // pairs fit the workgroup.  Over Goldilocks the four launches are flat at ~28 us and overtake at ~600 chunks: half the threshold
+        one = any && k.impl != IMPL_SAT32 && s.N / (2 * s.t + 1) <= k.fused_triplegen_max / (gold ? 2 : 1) && s.n == 3 * s.t + 1 && s.n <= 16;
+        break;
+    case ProtocolCall::FpMul: one = wave && s.N <= k.fused_fpmul_max && (4 + s.m) * s.n <= 4096; break;  // 4 + m operands per party in LDS
+    case ProtocolCall::TruncPr: one = wave && s.N <= k.fused_truncpr_max; break;
+    case ProtocolCall::Mul: one = wave && s.N <= k.fused_mul_max; break;
+    case ProtocolCall::RandBit:
+        // a chunk is t + 1 elements; both opens decode from exactly 2t + 1 senders, and the pairs of one open fit the workgroup
+        one = any && k.impl != IMPL_SAT32 && s.N / (s.t + 1) <= k.fused_randbit_max && s.n <= 16 && s.t >= 1;
+        break;
+    }
+    // the pair form: ahead from ~8 000 elements (tools/sweep_fused_fpmul.py); Goldilocks has none
+    return ProtocolPlan{one, lane_share(s.t + 2, 32, s.t), lane_share(s.t + 1, 64, s.t), (fpmul || mul) && !gold && s.N >= k.pair_decode_min};
+}
+
+}  // namespace hbmpc
