@@ -19,7 +19,9 @@
 //                  honeybadger/mod.rs:543-628, mul/multiplication.rs:417-426,102-139,57-100
 //
 // Host-side orchestration only: this file is a CLIENT of the hbmpc_dev_* entry points (it includes nothing but the public
-// header); every arithmetic step is a device call, buffers never leave HBM, the parties' all-to-all is a layout.
+// header and producer_route.hpp, the plain-C++ rule for the form the producers' calls take) and compiles with a host C++ compiler,
+// which is how tests/cpp/pipeline_calls_dump.cpp records its calls; every arithmetic step is a device call, buffers never leave HBM,
+// the parties' all-to-all is a layout.
 #include <cstring>
 #include <map>
 #include <memory>
@@ -27,6 +29,7 @@
 #include <vector>
 
 #include "../../include/hbmpc_hip.h"
+#include "producer_route.hpp"
 
 namespace {
 
@@ -39,58 +42,68 @@ struct PipeError {
         if (rc_ != ShareSuccess) throw PipeError{rc_}; \
     } while (0)
 
-// the two fields' entry points behind one signature (elements are 32-byte U256 or 8-byte uint64_t)
+// the two fields' entry points behind one signature (elements are 32-byte U256 or 8-byte uint64_t): every cast of a two-field buffer is here
 struct Calls {
     bool gl;
     size_t eb;  // bytes per element
+    using G = uint64_t;
+    using F = U256;
     ShareErrorCode compute_shares(hbmpc_ctx* c, const void* co, size_t B, size_t n, size_t d, void* out, void* s) const {
-        return gl ? hbmpc_gl_dev_compute_shares(c, (const uint64_t*)co, B, n, d, (uint64_t*)out, s)
-                  : hbmpc_dev_compute_shares(c, (const U256*)co, B, n, d, (U256*)out, s);
+        return gl ? hbmpc_gl_dev_compute_shares(c, (const G*)co, B, n, d, (G*)out, s) : hbmpc_dev_compute_shares(c, (const F*)co, B, n, d, (F*)out, s);
     }
-    ShareErrorCode apply_rows(hbmpc_ctx* c, const void* x, size_t stride, size_t G, size_t n, size_t d, void* tmp, void* y, void* s) const {
-        return gl ? hbmpc_gl_dev_vandermonde_apply_rows(c, (const uint64_t*)x, stride, G, n, d, (uint64_t*)tmp, (uint64_t*)y, s)
-                  : hbmpc_dev_vandermonde_apply_rows(c, (const U256*)x, stride, G, n, d, (U256*)tmp, (U256*)y, s);
+    ShareErrorCode apply_parties(hbmpc_ctx* c, const void* x, size_t B, size_t n, size_t d, size_t parties, void* y, void* s) const {
+        return gl ? hbmpc_gl_dev_vandermonde_apply_parties(c, (const G*)x, B, n, d, parties, (G*)y, s)
+                  : hbmpc_dev_vandermonde_apply_parties(c, (const F*)x, B, n, d, parties, (F*)y, s);
     }
-    ShareErrorCode apply_rows_lists(hbmpc_ctx* c, const void* x, size_t stride, size_t G, size_t n, size_t d, void* tmp, void* y, size_t row0,
+    ShareErrorCode apply_rows_lists(hbmpc_ctx* c, const void* x, size_t stride, size_t B, size_t n, size_t d, void* tmp, void* y, size_t row0,
                                     size_t rows, size_t K, const hbmpc_list_slice* sl, size_t nsl, void* s) const {
-        return gl ? hbmpc_gl_dev_vandermonde_apply_rows_lists(c, (const uint64_t*)x, stride, G, n, d, (uint64_t*)tmp, (uint64_t*)y, row0, rows, K, sl, nsl, s)
-                  : hbmpc_dev_vandermonde_apply_rows_lists(c, (const U256*)x, stride, G, n, d, (U256*)tmp, (U256*)y, row0, rows, K, sl, nsl, s);
+        return gl ? hbmpc_gl_dev_vandermonde_apply_rows_lists(c, (const G*)x, stride, B, n, d, (G*)tmp, (G*)y, row0, rows, K, sl, nsl, s)
+                  : hbmpc_dev_vandermonde_apply_rows_lists(c, (const F*)x, stride, B, n, d, (F*)tmp, (F*)y, row0, rows, K, sl, nsl, s);
     }
-    ShareErrorCode apply_rows_split(hbmpc_ctx* c, const void* x, size_t stride, size_t G, size_t n, size_t d, void* tmp, void* y, size_t row0,
+    ShareErrorCode apply_rows_split(hbmpc_ctx* c, const void* x, size_t stride, size_t B, size_t n, size_t d, void* tmp, void* y, size_t row0,
                                     size_t rows, size_t K, const hbmpc_list_slice* sl, size_t nsl, void* others, void* s) const {
-        return gl ? hbmpc_gl_dev_vandermonde_apply_rows_split(c, (const uint64_t*)x, stride, G, n, d, (uint64_t*)tmp, (uint64_t*)y, row0, rows, K, sl, nsl,
-                                                              (uint64_t*)others, s)
-                  : hbmpc_dev_vandermonde_apply_rows_split(c, (const U256*)x, stride, G, n, d, (U256*)tmp, (U256*)y, row0, rows, K, sl, nsl, (U256*)others, s);
+        return gl ? hbmpc_gl_dev_vandermonde_apply_rows_split(c, (const G*)x, stride, B, n, d, (G*)tmp, (G*)y, row0, rows, K, sl, nsl, (G*)others, s)
+                  : hbmpc_dev_vandermonde_apply_rows_split(c, (const F*)x, stride, B, n, d, (F*)tmp, (F*)y, row0, rows, K, sl, nsl, (F*)others, s);
     }
-    ShareErrorCode interpolate_c0(hbmpc_ctx* c, const size_t* ids, size_t S, const void* ev, size_t stride, size_t G, size_t n, void* tmp,
+    ShareErrorCode interpolate_c0(hbmpc_ctx* c, const size_t* ids, size_t S, const void* ev, size_t stride, size_t B, size_t n, void* tmp,
                                   void* c0, uint32_t* deg, void* s) const {
-        return gl ? hbmpc_gl_dev_batch_interpolate_c0(c, ids, S, (const uint64_t*)ev, stride, G, n, (uint64_t*)tmp, (uint64_t*)c0, deg, s)
-                  : hbmpc_dev_batch_interpolate_c0(c, ids, S, (const U256*)ev, stride, G, n, (U256*)tmp, (U256*)c0, deg, s);
+        return gl ? hbmpc_gl_dev_batch_interpolate_c0(c, ids, S, (const G*)ev, stride, B, n, (G*)tmp, (G*)c0, deg, s)
+                  : hbmpc_dev_batch_interpolate_c0(c, ids, S, (const F*)ev, stride, B, n, (F*)tmp, (F*)c0, deg, s);
     }
-    ShareErrorCode recover_strided(hbmpc_ctx* c, const size_t* ids, size_t S, const void* ev, size_t stride, size_t G, size_t n, size_t d,
-                                   size_t t, int p0, void* out, uint32_t* nco, uint8_t* st, hbmpc_recover_summary* sm, void* s) const {
-        return gl ? hbmpc_gl_dev_batch_recover_strided(c, ids, S, (const uint64_t*)ev, stride, G, n, d, t, p0, (uint64_t*)out, nco, st, sm, s)
-                  : hbmpc_dev_batch_recover_strided(c, ids, S, (const U256*)ev, stride, G, n, d, t, p0, (U256*)out, nco, st, sm, s);
+    // Fr only: Goldilocks has no selective decode
+    ShareErrorCode interpolate_degree_check(hbmpc_ctx* c, const size_t* ids, size_t S, const void* ev, size_t stride, size_t B, size_t n, size_t d,
+                                            size_t groups, size_t group_stride, void* ws, void* sel, uint8_t* st, void* s) const {
+        return gl ? TypeMismatch
+                  : hbmpc_dev_interpolate_degree_check_strided(c, ids, S, (const F*)ev, stride, B, n, d, groups, group_stride, (F*)ws, (F*)sel, st, s);
     }
-    ShareErrorCode recover(hbmpc_ctx* c, const size_t* ids, size_t S, const void* ev, size_t G, size_t n, size_t d, size_t t, void* out,
-                           uint32_t* nco, uint8_t* st, hbmpc_recover_summary* sm, void* s) const {
-        return gl ? hbmpc_gl_dev_batch_recover(c, ids, S, (const uint64_t*)ev, G, n, d, t, (uint64_t*)out, nco, st, sm, s)
-                  : hbmpc_dev_batch_recover(c, ids, S, (const U256*)ev, G, n, d, t, (U256*)out, nco, st, sm, s);
+    ShareErrorCode recover_check_degree(hbmpc_ctx* c, const size_t* ids, size_t S, const void* ev, size_t stride, size_t B, size_t n, size_t t,
+                                        size_t groups, size_t group_stride, void* ws, uint8_t* st, hbmpc_recover_summary* sm, uint32_t* bad,
+                                        void* s) const {
+        return gl ? hbmpc_gl_dev_recover_check_degree_strided(c, ids, S, (const G*)ev, stride, B, n, t, groups, group_stride, (G*)ws, st, sm, bad, s)
+                  : hbmpc_dev_recover_check_degree_strided(c, ids, S, (const F*)ev, stride, B, n, t, groups, group_stride, (F*)ws, st, sm, bad, s);
     }
-    ShareErrorCode interpolate(hbmpc_ctx* c, const size_t* ids, size_t S, const void* ev, size_t stride, size_t G, size_t n, void* out,
-                               uint32_t* deg, void* s) const {
-        return gl ? hbmpc_gl_dev_batch_interpolate(c, ids, S, (const uint64_t*)ev, stride, G, n, (uint64_t*)out, deg, s)
-                  : hbmpc_dev_batch_interpolate(c, ids, S, (const U256*)ev, stride, G, n, (U256*)out, deg, s);
+    ShareErrorCode triplegen_parties(hbmpc_ctx* c, const void* a, const void* b, const void* r2t, const void* rt, size_t N, size_t n, size_t t, void* Y,
+                                     void* Z, void* opened, void* out, uint8_t* st, hbmpc_recover_summary* sf, hbmpc_recover_summary* sm, void* s) const {
+        return gl ? hbmpc_gl_dev_triplegen_parties(c, (const G*)a, (const G*)b, (const G*)r2t, (const G*)rt, N, n, t, (G*)Y, (G*)Z, (G*)opened, (G*)out, st,
+                                                   sf, sm, s)
+                  : hbmpc_dev_triplegen_parties(c, (const F*)a, (const F*)b, (const F*)r2t, (const F*)rt, N, n, t, (F*)Y, (F*)Z, (F*)opened, (F*)out, st, sf,
+                                                sm, s);
     }
-    ShareErrorCode triple_encode(hbmpc_ctx* c, const void* a, const void* b, const void* r, size_t G, size_t n, size_t d, size_t parties,
-                                 void* tmp, void* y, void* s) const {
-        return gl ? hbmpc_gl_dev_triple_encode_parties(c, (const uint64_t*)a, (const uint64_t*)b, (const uint64_t*)r, G, n, d, parties,
-                                                       (uint64_t*)tmp, (uint64_t*)y, s)
-                  : hbmpc_dev_triple_encode_parties(c, (const U256*)a, (const U256*)b, (const U256*)r, G, n, d, parties, (U256*)tmp, (U256*)y, s);
+    ShareErrorCode mul_parties(hbmpc_ctx* c, const size_t* ids, size_t S, const void* ta, const void* tb, const void* tc, const void* x, const void* y,
+                               size_t N, size_t n, size_t t, void* desh, void* deop, void* out, uint8_t* st, hbmpc_recover_summary* sm, void* s) const {
+        return gl ? hbmpc_gl_dev_mul_parties(c, ids, S, (const G*)ta, (const G*)tb, (const G*)tc, (const G*)x, (const G*)y, N, n, t, (G*)desh, (G*)deop,
+                                             (G*)out, st, sm, s)
+                  : hbmpc_dev_mul_parties(c, ids, S, (const F*)ta, (const F*)tb, (const F*)tc, (const F*)x, (const F*)y, N, n, t, (F*)desh, (F*)deop,
+                                          (F*)out, st, sm, s);
     }
-    ShareErrorCode triple_finalize(hbmpc_ctx* c, const void* rt, const void* opened, size_t N, size_t parties, void* out, void* s) const {
-        return gl ? hbmpc_gl_dev_triple_finalize_parties(c, (const uint64_t*)rt, (const uint64_t*)opened, N, parties, (uint64_t*)out, s)
-                  : hbmpc_dev_triple_finalize_parties(c, (const U256*)rt, (const U256*)opened, N, parties, (U256*)out, s);
+    ShareErrorCode randbit_parties(hbmpc_ctx* c, const void* a, const void* ta, const void* tb, const void* tc, size_t N, size_t n, size_t t, void* desh,
+                                   void* Y, void* Z, void* deop, void* sq, void* sqop, void* out, uint8_t* st, uint8_t* rde, uint8_t* rsq,
+                                   hbmpc_recover_summary* s1, hbmpc_recover_summary* s2, hbmpc_recover_summary* s3, hbmpc_recover_summary* s4,
+                                   hbmpc_randbit_summary* rb, void* s) const {
+        return gl ? hbmpc_gl_dev_randbit_parties(c, (const G*)a, (const G*)ta, (const G*)tb, (const G*)tc, N, n, t, (G*)desh, (G*)Y, (G*)Z, (G*)deop, (G*)sq,
+                                                 (G*)sqop, (G*)out, st, rde, rsq, s1, s2, s3, s4, rb, s)
+                  : hbmpc_dev_randbit_parties(c, (const F*)a, (const F*)ta, (const F*)tb, (const F*)tc, N, n, t, (F*)desh, (F*)Y, (F*)Z, (F*)deop, (F*)sq,
+                                              (F*)sqop, (F*)out, st, rde, rsq, s1, s2, s3, s4, rb, s);
     }
 };
 
@@ -117,8 +130,8 @@ struct hbmpc_pipe {
     uint32_t* bad = nullptr;                // producers: {verifier checks that failed, first failing batch element}
 
     hbmpc_pipe(hbmpc_ctx* c, void* s) : ctx(c), stream(s) {
-        f.gl = hbmpc_field_of(c) == Goldilocks64;
-        f.eb = f.gl ? 8 : 32;
+        const bool gl = hbmpc_field_of(c) == Goldilocks64;
+        f = Calls{gl, (size_t)(gl ? 8 : 32)};
     }
     virtual ~hbmpc_pipe() {
         hbmpc_graph_destroy(graph);
@@ -183,12 +196,7 @@ struct TripleGen : hbmpc_pipe {
     }
     void run() override {
         // one call for the whole step: one launch for a small batch, four otherwise (hbmpc_[gl_]dev_triplegen_parties)
-        if (f.gl)
-            PL(hbmpc_gl_dev_triplegen_parties(ctx, (const uint64_t*)a, (const uint64_t*)b, (const uint64_t*)r2t, (const uint64_t*)rt, N, n, t, (uint64_t*)Y,
-                                              (uint64_t*)Z, (uint64_t*)opened, (uint64_t*)c, status, summ_first, summ, stream));
-        else
-            PL(hbmpc_dev_triplegen_parties(ctx, (const U256*)a, (const U256*)b, (const U256*)r2t, (const U256*)rt, N, n, t, (U256*)Y, (U256*)Z,
-                                           (U256*)opened, (U256*)c, status, summ_first, summ, stream));
+        PL(f.triplegen_parties(ctx, a, b, r2t, rt, N, n, t, Y, Z, opened, c, status, summ_first, summ, stream));
         check_summary(summ_first);
         check_summary(summ);
     }
@@ -286,12 +294,7 @@ struct Mul : hbmpc_pipe {
     }
     void run() override {
         // one launch for a small batch over Fr, three otherwise (hbmpc_[gl_]dev_mul_parties); checked mode looks at the open's summary afterwards
-        if (f.gl)
-            PL(hbmpc_gl_dev_mul_parties(ctx, ids.data(), ids.size(), (const uint64_t*)ta, (const uint64_t*)tb, (const uint64_t*)tc, (const uint64_t*)x,
-                                        (const uint64_t*)y, N, n, t, (uint64_t*)desh, (uint64_t*)deop, (uint64_t*)out, status, summ, stream));
-        else
-            PL(hbmpc_dev_mul_parties(ctx, ids.data(), ids.size(), (const U256*)ta, (const U256*)tb, (const U256*)tc, (const U256*)x, (const U256*)y, N, n,
-                                     t, (U256*)desh, (U256*)deop, (U256*)out, status, summ, stream));
+        PL(f.mul_parties(ctx, ids.data(), ids.size(), ta, tb, tc, x, y, N, n, t, desh, deop, out, status, summ, stream));
         check_summary(summ);
     }
 };
@@ -302,39 +305,23 @@ struct Mul : hbmpc_pipe {
 // sends verifier i is y[i][j K .. j K + K): a strided sender row, nothing is copied.
 struct Producer : hbmpc_pipe {
     size_t n, t, K;
-    // all verifiers' columns in ONE launch of the wave-per-chunk decode (groups): ahead of the other forms up to this many chunks -- at 6 144 and
-    // 8 192 (n = 7 at the node's 1 536 / 2 048 columns) the party-major form below takes 0.070 / 0.037 ms against 0.121 / 0.071
-    // (profiles/r04_protocol_batch_sizes.txt)
-    size_t grouped_max = 4096;
-    // above: a launch per dealer.  Measured (tools/time_dealers_together.py, n = 16, degree 5): 0.037 ms against 0.146 at 16 000 polynomials per
-    // dealer, 0.159 / 0.295 at 65 536, 0.613 / 0.787 at 262 144 -- a launch of one dealer's batch spends a visible part of its time filling and
-    // draining the chip until the batch has some 10^6 polynomials
-    size_t dealers_together_max = ((size_t)1 << 20) - 1;
-    Producer(hbmpc_ctx* cx, size_t n_, size_t t_, size_t K_, void* s) : hbmpc_pipe(cx, s), n(n_), t(t_), K(K_) {}
-    void deal_one(const unsigned char* coeffs, size_t deg, unsigned char* S) {
-        // compute_shares of every dealer's K polynomials: coeffs [dealer][K][deg + 1] -> S [dealer][recipient][K] is the party-batched
-        // encode's layout (hbmpc_dev_vandermonde_apply_parties).  A launch per dealer is at the memory rate only from some 10^6 polynomials;
-        // below that all dealers go into ONE launch over (dealer, polynomial), whatever kernel family the size takes: the wave-per-chunk
-        // kernels up to 2 048 chunks, the point-pair matrix-core kernel on domains of 8 / 16 points from 16 384, the lane kernels elsewhere.
-        // At the node's batch sizes (K ~ 7 000 .. 15 000, n = 16) 16 launches of 10 us each were 45 % of the producers' time
-        // (profiles/r04_protocol_batch_sizes.txt); at small ones (n = 16, 367 polynomials per dealer) one launch takes 12.6 us against
-        // 23.7 for slices that stay within the wave-per-chunk kernels' range, at 1 024 polynomials 13.2 against 48.7.
-        auto together = [&](size_t p, size_t cnt) {
+    bool lists_in_kernel;  // does the mixing step write its lists from the kernel that computes them?  (a fact of the context: asked once)
+    hbmpc::VerifyPlan v;   // the form of the verifiers' calls and the workspace it needs: what the arena is sized from and what finish() enqueues
+    Producer(hbmpc_ctx* cx, size_t n_, size_t t_, size_t K_, void* s) : hbmpc_pipe(cx, s), n(n_), t(t_), K(K_) {
+        // the degree-2t sharing (RanDouSha) and the 2t verifiers (RanSha) need 2t + 1 <= n points; before anything is sized from n - 2t
+        if (n <= 2 * t || K == 0) throw PipeError{InvalidInput};
+        int yes = 0;
+        PL(hbmpc_dev_apply_rows_lists_in_kernel(ctx, n * K, n, n - 1, &yes));
+        lists_in_kernel = yes != 0;
+    }
+    // compute_shares of every dealer's K polynomials: coeffs [dealer][K][deg + 1] -> S [dealer][recipient][K], `per` dealers to a call (plan_deal)
+    void deal_one(const unsigned char* coeffs, size_t deg, size_t per, unsigned char* S) {
+        for (size_t p = 0; p < n; p += per) {
             const unsigned char* co = coeffs + p * K * (deg + 1) * f.eb;
             unsigned char* out = S + p * n * K * f.eb;
-            PL(f.gl ? hbmpc_gl_dev_vandermonde_apply_parties(ctx, (const uint64_t*)co, K, n, deg, cnt, (uint64_t*)out, stream)
-                    : hbmpc_dev_vandermonde_apply_parties(ctx, (const U256*)co, K, n, deg, cnt, (U256*)out, stream));
-        };
-        if (K <= dealers_together_max) {  // as many dealers per call as the one-launch form's 32-bit offsets allow (4 GiB of outputs, of inputs)
-            const size_t lim = ((size_t)1 << 32) - 1;
-            const size_t per = std::min(n, std::min(lim / (n * K * f.eb), lim / (K * (deg + 1) * f.eb)));
-            if (per >= 2) {
-                for (size_t p = 0; p < n; p += per) together(p, n - p < per ? n - p : per);
-                return;
-            }
+            if (per == 1) PL(f.compute_shares(ctx, co, K, n, deg, out, stream));
+            else PL(f.apply_parties(ctx, co, K, n, deg, n - p < per ? n - p : per, out, stream));
         }
-        for (size_t p = 0; p < n; ++p)  // dealer p: compute_shares of its K polynomials
-            PL(f.compute_shares(ctx, coeffs + p * K * (deg + 1) * f.eb, K, n, deg, S + p * n * K * f.eb, stream));
     }
     // The share of dealer p for (recipient, element) is row p of S: the n x n map reads the dealers' outputs in place (x is the
     // workspace of the shapes that have to be transposed first).  Rows [row0, row0 + rows) of the result are the parties' OUTPUT:
@@ -346,18 +333,9 @@ struct Producer : hbmpc_pipe {
         if (others) PL(f.apply_rows_split(ctx, S, n * K, n * K, n, n - 1, x, y, row0, rows, K, lists.data(), lists.size(), others, stream));
         else PL(f.apply_rows_lists(ctx, S, n * K, n * K, n, n - 1, x, y, row0, rows, K, lists.data(), lists.size(), stream));
     }
-    // Mid-size batches (the reference's own: some thousands of columns per dealer): one verifier's decode is a launch of ~10 us that
-    // does not fill the chip, and there are 2t (RanSha) or 2 (n - t - 1) (RanDouSha) of them.  Where the mixing kernel can write the
-    // verifiers' rows party-major, all verifiers of a kind are ONE decode over (verifier, column) chunks (profiles/r04_protocol_batch_sizes.txt).
-    // Measured ahead of a call per verifier up to 250 000 columns (n = 16: RanSha 0.742 -> 0.616 ms at 80 000, RanDouSha 4.39 -> 3.92 at 250 000), level
-    // with it at 699 050 (config 4's producers); from 2^19 columns on -- and where the party-major block would pass 4 GiB -- a call each, without the
-    // extra rows.  Shapes no list kernel covers (more than 16 parties; 9 .. 16 over Fr at small batches) pay one more pass for the party-major rows
-    // (k_rows_party_major): from three verifiers on that is still fewer launches.
-    bool verifiers_together(size_t nver) const {
-        int yes = 0;
-        if (nver < 2 || K >= ((size_t)1 << 19) || n * nver * K * f.eb >= ((size_t)1 << 32)) return false;
-        if (hbmpc_dev_apply_rows_lists_in_kernel(ctx, n * K, n, n - 1, &yes) != ShareSuccess) return false;
-        return yes != 0 || nver >= 3;
+    // call i's source: the party-major block where the form has one, the mixing call's rows otherwise
+    const unsigned char* source(size_t i, const unsigned char* y, const unsigned char* yv) const {
+        return (v.party_major ? yv : y) + (v.src0 + i * v.call_stride) * f.eb;
     }
     void run() override {
         deal();
@@ -369,93 +347,60 @@ struct Producer : hbmpc_pipe {
 // shares of the first verify_senders parties (0 = the default 2t + 1: the handler fires when that many have arrived,
 // share_gen.rs:497 -- with degree t a decode with no OEC round)
 struct RanSha : Producer {
-    size_t nout;
+    size_t nout, per;
     unsigned char *coeffs, *S, *x, *y, *yv = nullptr, *poly, *out;
     uint8_t* status;
-    bool grouped, together;
     std::vector<size_t> ids;
     std::vector<Slice> split;  // set by Preprocessing: where the output slices go instead of `out`
-    static size_t checked_nout(size_t n, size_t t, size_t K) {  // before the arena is sized from n - 2t
-        if (n <= 2 * t || K == 0) throw PipeError{InvalidInput};
-        return (n - 2 * t) * K;
-    }
     RanSha(hbmpc_ctx* cx, size_t n_, size_t t_, size_t K_, size_t verify_senders, void* s)
-        : Producer(cx, n_, t_, K_, s), nout(checked_nout(n_, t_, K_)) {
+        : Producer(cx, n_, t_, K_, s), nout((n_ - 2 * t_) * K_), per(hbmpc::plan_deal(f.eb, n_, K_, t_)) {
         if (verify_senders == 0) verify_senders = 2 * t + 1;
         if (verify_senders < 2 * t + 1 || verify_senders > n) throw PipeError{InvalidInput};
-        grouped = 2 * t * K <= grouped_max;  // the verifiers' columns fit one launch of the wave-per-chunk decode: workspace for all of them
-        together = !grouped && verify_senders == 2 * t + 1 && verifiers_together(2 * t);
-        const bool all = grouped || together;
-        const size_t poly_el = K * (all && 2 * t > t + 1 ? 2 * t : t + 1), status_b = all ? 2 * t * K + 1 : K;
-        arena((n * K * (t + 1) + 3 * n * n * K + (together ? 2 * t * n * K : 0) + poly_el + n * nout) * f.eb + status_b + (1 << 14));
+        v = hbmpc::plan_ransha(f.eb, n, t, K, verify_senders, lists_in_kernel);
+        arena((n * K * (t + 1) + 3 * n * n * K + v.yv_el + v.poly_el + n * nout) * f.eb + v.status_b + (1 << 14));
         coeffs = take("coeffs", n * K * (t + 1));  // [dealer][K][t + 1]
         S = take("S", n * n * K);                  // [dealer][recipient][K]
         x = take("x", n * n * K);
         y = take("y", n * n * K);                  // [row i][party][K]
-        if (together) yv = take("yv", 2 * t * n * K);  // [party][verifier i][K]
-        poly = take("poly", poly_el);
-        status = take_bytes("status", status_b, K);
+        if (v.yv_el) yv = take("yv", v.yv_el);     // [party][verifier i][K]
+        poly = take("poly", v.poly_el);
+        status = take_bytes("status", v.status_b, K);
         summ = reinterpret_cast<hbmpc_recover_summary*>(take_bytes("summary", 64, 16));
         bad = reinterpret_cast<uint32_t*>(take_bytes("bad", 64, 16));
         out = take("out", n * nout);               // [party][K][n - 2t]: the reference's output order (share_gen.rs:199-203)
         for (size_t i = 0; i < verify_senders; ++i) ids.push_back(i);
     }
-    void deal() override { deal_one(coeffs, t, S); }
+    void deal() override { deal_one(coeffs, t, per, S); }
     void finish() override {  // everything after the dealers' messages have arrived
         // rows 2t .. n - 1 of every batch element are the output, per party in the order [k][i - 2t]  (share_gen.rs:199-203)
         mix(S, x, y, 2 * t, n - 2 * t, split.empty() ? std::vector<Slice>{{out, nout, 0, K}} : split, yv);
         clear_bad();
-        // verifiers 0 .. 2t - 1: recover_secret of the K columns + exact-degree test (share_gen.rs:516-530); verifier i's sender rows are
-        // y + i n K: all of them in one call (one launch for a small batch: `grouped` sized the workspace for it)
-        const size_t nver = 2 * t;
-        if (nver == 0) return;
-        if (together) {  // sender j's row: yv + j nver K, verifier i's columns at i K inside it -- groups that follow each other
-            PL(f.gl ? hbmpc_gl_dev_recover_check_degree_strided(ctx, ids.data(), ids.size(), (const uint64_t*)yv, nver * K, K, n, t, nver, K, (uint64_t*)poly,
-                                                                status, summ, bad, stream)
-                    : hbmpc_dev_recover_check_degree_strided(ctx, ids.data(), ids.size(), (const U256*)yv, nver * K, K, n, t, nver, K, (U256*)poly, status, summ,
-                                                             bad, stream));
-            return;
-        }
-        if (grouped) {
-            PL(f.gl ? hbmpc_gl_dev_recover_check_degree_strided(ctx, ids.data(), ids.size(), (const uint64_t*)y, K, K, n, t, nver, n * K, (uint64_t*)poly,
-                                                                status, summ, bad, stream)
-                    : hbmpc_dev_recover_check_degree_strided(ctx, ids.data(), ids.size(), (const U256*)y, K, K, n, t, nver, n * K, (U256*)poly, status, summ,
-                                                             bad, stream));
-            return;
-        }
-        for (size_t i = 0; i < nver; ++i)
-            PL(f.gl ? hbmpc_gl_dev_recover_check_degree_strided(ctx, ids.data(), ids.size(), (const uint64_t*)(y + i * n * K * f.eb), K, K, n, t, 1, 0,
-                                                                (uint64_t*)poly, status, summ, bad, stream)
-                    : hbmpc_dev_recover_check_degree_strided(ctx, ids.data(), ids.size(), (const U256*)(y + i * n * K * f.eb), K, K, n, t, 1, 0, (U256*)poly,
-                                                             status, summ, bad, stream));
+        // verifiers 0 .. 2t - 1: recover_secret of the K columns + exact-degree test (share_gen.rs:516-530), in the calls the plan lays out
+        for (size_t i = 0; i < v.calls; ++i)
+            PL(f.recover_check_degree(ctx, ids.data(), ids.size(), source(i, y, yv), v.row_stride, v.columns, n, t, v.groups, v.group_stride, poly, status,
+                                      summ, bad, stream));
     }
 };
 
 // K batch elements per dealer -> (t + 1) K double sharings per party, verified by parties t + 1 .. n - 1, each of which
 // interpolates both polynomials through ALL n shares (ran_dou_sha/mod.rs:557-602)
 struct RanDouSha : Producer {
-    size_t nout;
+    size_t nout, per_t, per_2t;
     unsigned char *coeffs_t, *coeffs_2t, *S_t, *S_2t, *x, *y_t, *y_2t, *poly, *c0_t, *c0_2t, *out_t, *out_2t, *sel_t, *sel_2t, *st_t, *st_2t;
     unsigned char *yv_t = nullptr, *yv_2t = nullptr;
     uint32_t *deg_t, *deg_2t;
-    bool grouped, together;
     std::vector<size_t> ids;
     std::vector<Slice> split_t, split_2t;
-    static size_t checked_nout(size_t n, size_t t, size_t K) {
-        if (n <= 2 * t || K == 0) throw PipeError{InvalidInput};  // the degree-2t sharing needs 2t + 1 <= n points
-        return (t + 1) * K;
-    }
-    RanDouSha(hbmpc_ctx* cx, size_t n_, size_t t_, size_t K_, void* s) : Producer(cx, n_, t_, K_, s), nout(checked_nout(n_, t_, K_)) {
-        grouped = (n - t - 1) * K <= grouped_max && !f.gl;  // (Fr only) the verifiers' columns fit one launch of the wave-per-chunk decode: room for all their results
-        together = !grouped && 2 * t < n && verifiers_together(n - t - 1);
-        const size_t vr = grouped || together ? n - t - 1 : 1;
-        const size_t vc = together && f.gl ? vr : 1;  // Goldilocks has no selective decode: the verifiers' full interpolations, all in one call
-        arena((n * K * (3 * t + 2) + 5 * n * n * K + (together ? 2 * vr * n * K : 0) + vc * K * n + (2 * vc + 4 * vr) * K + 2 * n * nout) * f.eb +
-              (8 * vc + 2 * vr) * K + (1 << 14));
+    RanDouSha(hbmpc_ctx* cx, size_t n_, size_t t_, size_t K_, void* s)
+        : Producer(cx, n_, t_, K_, s), nout((t_ + 1) * K_), per_t(hbmpc::plan_deal(f.eb, n_, K_, t_)), per_2t(hbmpc::plan_deal(f.eb, n_, K_, 2 * t_)) {
+        v = hbmpc::plan_randousha(f.eb, n, t, K, lists_in_kernel);
+        const size_t vr = v.vr, vc = v.vc;
+        arena((n * K * (3 * t + 2) + 5 * n * n * K + 2 * v.yv_el + vc * K * n + (2 * vc + 4 * vr) * K + 2 * n * nout) * f.eb + (8 * vc + 2 * vr) * K +
+              (1 << 14));
         coeffs_t = take("coeffs_t", n * K * (t + 1)), coeffs_2t = take("coeffs_2t", n * K * (2 * t + 1));
         S_t = take("S_t", n * n * K), S_2t = take("S_2t", n * n * K);
         x = take("x", n * n * K), y_t = take("y_t", n * n * K), y_2t = take("y_2t", n * n * K);
-        if (together) yv_t = take("yv_t", vr * n * K), yv_2t = take("yv_2t", vr * n * K);  // [party][verifier][K]
+        if (v.yv_el) yv_t = take("yv_t", v.yv_el), yv_2t = take("yv_2t", v.yv_el);  // [party][verifier][K]
         poly = take("poly", vc * K * n);  // workspace of the verifier interpolations that have no c0-only kernel
         c0_t = take("c0_t", vc * K), c0_2t = take("c0_2t", vc * K);
         deg_t = reinterpret_cast<uint32_t*>(take_bytes("deg_t", 4 * vc * K, K)), deg_2t = reinterpret_cast<uint32_t*>(take_bytes("deg_2t", 4 * vc * K, K));
@@ -466,8 +411,8 @@ struct RanDouSha : Producer {
         for (size_t i = 0; i < n; ++i) ids.push_back(i);
     }
     void deal() override {  // DouShaNode::init_batch: both sharings of every secret
-        deal_one(coeffs_t, t, S_t);
-        deal_one(coeffs_2t, 2 * t, S_2t);
+        deal_one(coeffs_t, t, per_t, S_t);
+        deal_one(coeffs_2t, 2 * t, per_2t, S_2t);
     }
     void finish() override {
         // RanDouShaNode::init_batch steps 1, 2, 4-5: rows 0 .. t are the output, per party in the order [k][i]  (ran_dou_sha/mod.rs:314-331)
@@ -475,41 +420,19 @@ struct RanDouSha : Producer {
         mix(S_2t, x, y_2t, 0, t + 1, split_2t.empty() ? std::vector<Slice>{{out_2t, nout, 0, K}} : split_2t, yv_2t);
         clear_bad();
         // step 3: verifiers t + 1 .. n - 1 interpolate both sharings through all n shares and test the degrees and the constant terms
-        // (:586-602) -- they keep nothing else of them
-        const size_t nver = n - t - 1, v0 = (t + 1) * n * K * f.eb;  // verifier i's sender rows: y + i n K
-        if (together && f.gl) {  // the n senders' rows nver K apart: every verifier's interpolation in one call, the verdicts in one
-            PL(f.interpolate_c0(ctx, ids.data(), n, yv_t, nver * K, nver * K, n, poly, c0_t, deg_t, stream));
-            PL(f.interpolate_c0(ctx, ids.data(), n, yv_2t, nver * K, nver * K, n, poly, c0_2t, deg_2t, stream));
-            PL(hbmpc_dev_check_double_share_c0_columns(ctx, c0_t, deg_t, c0_2t, deg_2t, nver * K, K, t, bad, stream));
-            return;
-        }
-        if (together) {  // sender j's row: yv + j nver K, verifier i's columns at i K inside it -- groups that follow each other
-            PL(hbmpc_dev_interpolate_degree_check_strided(ctx, ids.data(), n, (const U256*)yv_t, nver * K, K, n, t, nver, K, (U256*)poly, (U256*)sel_t, st_t, stream));
-            PL(hbmpc_dev_interpolate_degree_check_strided(ctx, ids.data(), n, (const U256*)yv_2t, nver * K, K, n, 2 * t, nver, K, (U256*)poly, (U256*)sel_2t, st_2t,
-                                                          stream));
-            PL(hbmpc_dev_check_double_share_sel(ctx, sel_t, st_t, sel_2t, st_2t, nver * K, K, t, bad, stream));
-            return;
-        }
-        if (!f.gl && 2 * t < n && grouped) {  // all verifiers in one call each (hbmpc_dev_interpolate_degree_check_strided)
-            PL(hbmpc_dev_interpolate_degree_check_strided(ctx, ids.data(), n, (const U256*)(y_t + v0), K, K, n, t, nver, n * K, (U256*)poly, (U256*)sel_t, st_t,
-                                                          stream));
-            PL(hbmpc_dev_interpolate_degree_check_strided(ctx, ids.data(), n, (const U256*)(y_2t + v0), K, K, n, 2 * t, nver, n * K, (U256*)poly, (U256*)sel_2t,
-                                                          st_2t, stream));
-            PL(hbmpc_dev_check_double_share_sel(ctx, sel_t, st_t, sel_2t, st_2t, nver * K, K, t, bad, stream));
-            return;
-        }
-        for (size_t i = t + 1; i < n; ++i) {
-            if (!f.gl && 2 * t < n) {  // the two questions answered without the full interpolation
-                PL(hbmpc_dev_interpolate_degree_check_strided(ctx, ids.data(), n, (const U256*)(y_t + i * n * K * f.eb), K, K, n, t, 1, 0, (U256*)poly,
-                                                              (U256*)sel_t, st_t, stream));
-                PL(hbmpc_dev_interpolate_degree_check_strided(ctx, ids.data(), n, (const U256*)(y_2t + i * n * K * f.eb), K, K, n, 2 * t, 1, 0, (U256*)poly,
-                                                              (U256*)sel_2t, st_2t, stream));
-                PL(hbmpc_dev_check_double_share_sel(ctx, sel_t, st_t, sel_2t, st_2t, K, 0, t, bad, stream));
-                continue;
+        // (:586-602) -- they keep nothing else of them.  Each call of the plan: both interpolations, then the verdict on their results
+        for (size_t i = 0; i < v.calls; ++i) {
+            const unsigned char *ev_t = source(i, y_t, yv_t), *ev_2t = source(i, y_2t, yv_2t);
+            if (v.check == hbmpc::VerifyCheck::Selected) {  // the two questions answered without the full interpolation
+                PL(f.interpolate_degree_check(ctx, ids.data(), n, ev_t, v.row_stride, v.columns, n, t, v.groups, v.group_stride, poly, sel_t, st_t, stream));
+                PL(f.interpolate_degree_check(ctx, ids.data(), n, ev_2t, v.row_stride, v.columns, n, 2 * t, v.groups, v.group_stride, poly, sel_2t, st_2t,
+                                              stream));
+                PL(hbmpc_dev_check_double_share_sel(ctx, sel_t, st_t, sel_2t, st_2t, v.verdict_G, v.verdict_columns, t, bad, stream));
+            } else {
+                PL(f.interpolate_c0(ctx, ids.data(), n, ev_t, v.row_stride, v.columns, n, poly, c0_t, deg_t, stream));
+                PL(f.interpolate_c0(ctx, ids.data(), n, ev_2t, v.row_stride, v.columns, n, poly, c0_2t, deg_2t, stream));
+                PL(hbmpc_dev_check_double_share_c0_columns(ctx, c0_t, deg_t, c0_2t, deg_2t, v.verdict_G, v.verdict_columns, t, bad, stream));
             }
-            PL(f.interpolate_c0(ctx, ids.data(), n, y_t + i * n * K * f.eb, K, K, n, poly, c0_t, deg_t, stream));
-            PL(f.interpolate_c0(ctx, ids.data(), n, y_2t + i * n * K * f.eb, K, K, n, poly, c0_2t, deg_2t, stream));
-            PL(hbmpc_dev_check_double_share_c0(ctx, c0_t, deg_t, c0_2t, deg_2t, K, t, bad, stream));
         }
     }
 };
@@ -596,14 +519,8 @@ struct RandBit : hbmpc_pipe {
     }
     void run() override {
         // one call for the whole protocol: one launch for a small batch, nine otherwise (hbmpc_[gl_]dev_randbit_parties)
-        if (f.gl)
-            PL(hbmpc_gl_dev_randbit_parties(ctx, (const uint64_t*)a, (const uint64_t*)ta, (const uint64_t*)tb, (const uint64_t*)tc, N, n, t, (uint64_t*)desh,
-                                            (uint64_t*)Y, (uint64_t*)Z, (uint64_t*)deop, (uint64_t*)sq, (uint64_t*)sqop, (uint64_t*)out, status, rst_de, rst_sq,
-                                            sm_de_first, sm_de, sm_sq_first, summ, rb, stream));
-        else
-            PL(hbmpc_dev_randbit_parties(ctx, (const U256*)a, (const U256*)ta, (const U256*)tb, (const U256*)tc, N, n, t, (U256*)desh, (U256*)Y, (U256*)Z,
-                                         (U256*)deop, (U256*)sq, (U256*)sqop, (U256*)out, status, rst_de, rst_sq, sm_de_first, sm_de, sm_sq_first, summ, rb,
-                                         stream));
+        PL(f.randbit_parties(ctx, a, ta, tb, tc, N, n, t, desh, Y, Z, deop, sq, sqop, out, status, rst_de, rst_sq, sm_de_first, sm_de, sm_sq_first, summ,
+                             rb, stream));
         if (!checked) return;
         // the opens' `?` in their order, then phase 2's (rand_bit.rs:198-207): the first summary that failed decides, read after ONE
         // synchronisation (the later steps have run by then)

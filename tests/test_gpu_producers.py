@@ -210,7 +210,7 @@ def test_producers_at_a_size_that_takes_the_large_batch_kernels(K):
 def test_producers_at_the_batch_sizes_of_the_reference_node(field, n, t, K):
     """Some thousands of columns per dealer (the reference node's own batches, honeybadger/mod.rs:106-120): the dealers' encodes are one
     launch over (dealer, polynomial), the verifiers' rows are party-major and every kind of verifier is ONE decode over (verifier, column)
-    chunks (capi_pipelines.hip: Producer::verifiers_together; over Goldilocks and on 4-point domains through k_rows_party_major and the
+    chunks (producer_route.hpp: verifiers_together; over Goldilocks and on 4-point domains through k_rows_party_major and the
     full interpolations).  Sampled columns of every party's outputs against the oracle, the verdicts, tampering caught with its column."""
     from oracle import cref as O
     S, to_dev, to_int = _field(field)
@@ -276,6 +276,46 @@ def test_producers_at_the_batch_sizes_of_the_reference_node(field, n, t, K):
         bad, first = rd._bad()
         assert bad == n - (t + 1) and first == k_bad
         rd.close()
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("field", ["fr", "goldilocks"])
+def test_ransha_together_and_per_verifier_forms_write_the_same_bytes(field):
+    """n = 7, t = 2, K = 1025: 2 t K = 4100 columns are past the grouped form's 4096 (producer_route.hpp: kGroupedMax), so the default
+    2t + 1 senders take the together form (four verifiers, party-major rows) and verify_senders = 7 the call per verifier, with OEC rounds
+    available -- the form no smaller test reaches.  Same coefficients: both verdicts pass, the whole outputs are equal byte for byte, and
+    twelve sampled columns plus the first and the last equal the oracle's.  No tampering here: with all seven senders one wrong share is
+    corrected, as the reference would."""
+    from oracle import cref as O
+    S, to_dev, to_int = _field(field)
+    gl = field != "fr"
+    n, t, K = 7, 2, 1025
+    pkg = load_package()
+    eng = pkg.Engine(0, field="goldilocks" if gl else "fr")
+    rng = random.Random(1025)
+    sample = sorted(rng.sample(range(1, K - 1), 12) + [0, K - 1])
+    ints = (lambda a: [int(x) for x in a.reshape(-1)]) if gl else (lambda a: u256_to_ints(np.ascontiguousarray(a).reshape(-1, 4)))
+    try:
+        if gl:
+            co = np.random.default_rng(1025).integers(0, S.R_MOD, size=(n, K, t + 1), dtype=np.uint64)
+        else:
+            co = O.fill_random(1025, n * K * (t + 1)).reshape(n, K, t + 1, 4)
+        outs = []
+        for senders in (None, n):
+            rs = pkg.pipelines.RanSha(eng, n, t, K, verify_senders=senders)
+            try:
+                rs.upload(co)
+                rs.run(check=True)
+                outs.append(rs.download().copy())
+            finally:
+                rs.close()
+        assert outs[0].tobytes() == outs[1].tobytes()
+        want, ok = S.ransha([[ints(co[p, k]) for k in sample] for p in range(n)], n, t)
+        assert all(ok)
+        got = outs[0].reshape((n, K, n - 2 * t) + (() if gl else (4,)))
+        for j in range(n):
+            assert ints(got[j, sample]) == want[j], j
     finally:
         eng.close()
 

@@ -1,5 +1,5 @@
 """The dealers' encodes of the producers: hbmpc_dev_vandermonde_apply_parties over all n dealers in one call against a
-hbmpc_dev_compute_shares call per dealer, n = 16, degree t and 2t, K polynomials per dealer -- where Producer::dealers_together_max comes from."""
+hbmpc_dev_compute_shares call per dealer, n = 16, degree t and 2t, K polynomials per dealer -- where kDealersTogetherMax (csrc/producer_route.hpp) comes from."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
