@@ -564,8 +564,9 @@ ShareErrorCode hbmpc_dev_triplegen_parties(hbmpc_ctx* ctx, const U256* a, const 
  * With exactly 2t + 1 senders (what the reference opens from: multiplication.rs:388, truncpr.rs:202) and at most
  * hbmpc_set_fused_fpmul elements (default 2048) the call is ONE launch, a wave per element (csrc/kernels_fpmul_wave.hpp: at these
  * sizes a multiplication is bound by launches and by a lone wave's chain of multiplications per step, not by bytes); otherwise it
- * is the five launches hbmpc_dev_beaver_open_shares_paired, hbmpc_dev_batch_recover_p0 (2 N values per sender),
- * hbmpc_dev_fpmul_middle, hbmpc_dev_batch_recover_p0, hbmpc_dev_truncpr_finalize_parties -- the first two as one from
+ * is the five launches hbmpc_dev_beaver_open_shares_paired, hbmpc_dev_batch_recover_slots (P(0), 2 N values per sender),
+ * hbmpc_dev_fpmul_middle, hbmpc_dev_batch_recover_slots (P(0)), hbmpc_dev_truncpr_finalize_parties -- both decodes read every
+ * sender's row in place at its party id, as hbmpc_dev_mul_parties' does -- the first two as one from
  * hbmpc_set_fpmul_pair_decode elements on (default 8192: the decode forms a - x and b - y of its 2t + 1 senders as it loads them).
  * Every output buffer holds the same bytes in every form; de_sh_ws [party][2][N] is the workspace of the five-launch form (contents
  * unspecified afterwards). */

@@ -2224,7 +2224,8 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
     if (!ctx) return InvalidInput;
     REQ_FR(ctx);
     if (!truncpr_params_ok(ctx, TP_ALL, k, m)) return InvalidInput;
-    if (!a || !b || !c || !x || !y || !r_int || (m && !r_bits) || !de_sh_ws || !de_out || !z_out || !r_dash_out || !open_sh_out || !c_open_out || !d_out)
+    if (!sender_ids || !a || !b || !c || !x || !y || !r_int || (m && !r_bits) || !de_sh_ws || !de_out || !z_out || !r_dash_out || !open_sh_out ||
+        !c_open_out || !d_out)
         return fail(ctx, InvalidInput, "null buffer");
     if (!batch_in_range(ctx, N, n)) return InvalidInput;
     const ProtocolPlan plan = plan_protocol(protocol_knobs(ctx), {ProtocolCall::FpMul, N, n, t, S, m});
@@ -2254,12 +2255,14 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
                                       [&] { launch_fpmul_wave(fa, ctx->device, s, false); });
         }
     }
-    ShareErrorCode rc = open_beaver_pair(ctx, plan.pair_first, false, sender_ids, S, a, b, x, y, N, n, t, de_sh_ws, de_out, status_out, summary_first_dev, stream);
+    // sender_ids are party ids and de_sh_ws, open_sh_out are [party][..], so both opens read every sender's row in place at its id (the slots form)
+    ShareErrorCode rc = open_beaver_pair(ctx, plan.pair_first, true, sender_ids, S, a, b, x, y, N, n, t, de_sh_ws, de_out, status_out, summary_first_dev, stream);
     if (rc != ShareSuccess) return rc;
     // finalize_mul (:57-100), r' (truncpr.rs:277-283), the share TruncPr opens (:294-297), its open (truncpr.rs:215), the last step (:216-220)
     rc = hbmpc_dev_fpmul_middle(ctx, c, x, y, de_out, de_out + N, r_bits, r_int, k, m, N, n, z_out, r_dash_out, open_sh_out, stream);
     if (rc != ShareSuccess) return rc;
-    rc = hbmpc_dev_batch_recover_p0(ctx, sender_ids, S, open_sh_out, N, n, t, t, c_open_out, status_out, summary_dev, stream);
+    rc = batch_recover_dev(ctx, {.sender_ids = sender_ids, .S = S, .evals = open_sh_out, .G = N, .n = n, .d = t, .t = t, .out = c_open_out,
+                                 .status = status_out, .summary = summary_dev, .p0 = true, .stream = stream, .slots = sender_ids});
     if (rc != ShareSuccess) return rc;
     return hbmpc_dev_truncpr_finalize_parties(ctx, z_out, r_dash_out, c_open_out, m, N, n, d_out, stream);
 }

@@ -13,6 +13,7 @@ from __graft_entry__ import ROOT, load_package
 from oracle import cref as O
 from oracle import cref_gl as OG
 from oracle import spec as S
+from tests import sender_sets as SS
 
 pytestmark = pytest.mark.gpu
 FORMS = (("one", 1 << 20), ("multi", 0))      # hbmpc_set_fused_mul: always (where the call qualifies) / never
@@ -188,7 +189,7 @@ def raw_call(eng, mp, ids, n, t, N, **kw):
     return eng.dev_mul_parties(list(ids), b["ta"], b["tb"], b["tc"], b["x"], b["y"], N, n, t, b["desh"], b["deop"], b["out"], b["status"], b["summary"])
 
 
-@pytest.mark.parametrize("n,t,N,ids", [(7, 2, 30, (6, 1, 3, 0, 4)), (9, 2, 20, (8, 2, 5, 7, 0))])
+@pytest.mark.parametrize("n,t,N,ids", [(7, 2, 30, (6, 1, 3, 0, 4)), (9, 2, 20, (8, 2, 5, 7, 0)), (31, 10, 18, SS.sender_set(31, 10))])
 def test_sender_sets(pkg_eng, n, t, N, ids):
     """sender_ids are party ids, unsorted and not a prefix: both forms open from exactly those parties' shares.  A party outside
     the set holds a wrong share of a at one element: nothing may change."""

@@ -9,6 +9,7 @@ from __graft_entry__ import load_package
 from oracle import cref as O
 from oracle import spec as S
 from tests import golden_util as GU
+from tests import sender_sets as SS
 
 pytestmark = pytest.mark.gpu
 R = S.R_MOD
@@ -49,13 +50,15 @@ def random_inputs(n, t, N, m, seed, with_w):
 
 
 def expected(ins, n, t, N, k, m, senders):
-    """the composition of oracle calls and big ints that the call replaces: c, r', open_sh per party, the open, the output"""
+    """the composition of oracle calls and big ints that the call replaces: c, r', open_sh per party, the open, the output.
+    senders: a count (the open is from parties 0 .. senders - 1) or the list of the parties whose shares are opened, in arrival order"""
+    ids = list(range(senders)) if isinstance(senders, (int, np.integer)) else list(senders)
     a, w = ins["a"], ins["w"]
     v = np.stack([O.fr_binop("mul", a[p], w) for p in range(n)]) if w is not None else a
     rd = np.stack([O.truncpr_rdash(np.ascontiguousarray(ins["rbits"][p]), m)[1] for p in range(n)])
     vi, ri, rdi = O.u256_to_ints(v), O.u256_to_ints(ins["rint"]), O.u256_to_ints(rd)
     osh = O.ints_to_u256([[(vi[p][i] + (1 << (k - 1)) + (ri[p][i] << m) + rdi[p][i]) % R for i in range(N)] for p in range(n)])  # truncpr.rs:275-297
-    rc, cop, st = O.batch_recover_p0(list(range(senders)), np.ascontiguousarray(osh[:senders]), n, t, t)   # a failed chunk: zero, status = its error
+    rc, cop, st = O.batch_recover_p0(ids, np.ascontiguousarray(osh[ids]), n, t, t)   # a failed chunk: zero, status = its error
     out = np.stack([O.truncpr_finalize(v[p], rd[p], cop, m)[1] for p in range(n)])
     return {"c": v, "rdash": rd, "osh": osh, "cop": cop, "out": out, "status": st, "rc": rc}
 
@@ -310,6 +313,57 @@ def test_sender_rows_follow_the_decode_call(pkg_eng):
     finally:
         eng.set_fused_truncpr(pkg.hbmpc.FUSED_TRUNCPR_DEFAULT)
         tp.close()
+
+
+@pytest.mark.parametrize("with_w", [False, True], ids=["truncpr", "fpdivconst"])
+@pytest.mark.parametrize("n,t,S", [(7, 2, 5), (7, 2, 6), (16, 5, 11)])
+def test_sender_sets(pkg_eng, n, t, S, with_w):
+    """the sets of tests/sender_sets.py -- unsorted, with party n - 1 and an id >= S, a low party left out -- so that a kernel with the
+    prefix's table, or one that ignores the ids, opens something else at every element (tests/test_sender_sets.py).  Row s of the
+    arrays holds the share of sender_ids[s]; the rows behind them hold the parties outside the set, whose shares of a and r_int
+    are wrong throughout.  Honest senders, then one lying behind a verify row and one behind the P(0) row: from 2t + 1 senders
+    exactly their elements fail in both forms, from 2t + 2 (three launches) they are repaired."""
+    pkg, eng = pkg_eng
+    N, k, m = 20, 32, 8
+    ids = SS.sender_set(n, t, S)
+    perm = list(ids) + SS.outsiders(n, ids)
+    ins = SS.with_wrong_outsider(random_inputs(n, t, N, m, 9000 + n + S, with_w), n, ids, ("a", "rint"), every=True)
+    honest = expected(ins, n, t, N, k, m, ids)
+    lied, bad = SS.truncpr_with_liars(ins, ids, t)
+    names = (("c",) if with_w else ()) + ("rdash", "osh", "out")
+    try:
+        for case, case_ins in (("honest", ins), ("liars", lied)):
+            want = expected(case_ins, n, t, N, k, m, ids)
+            assert np.flatnonzero(want["status"]).tolist() == ([] if case == "honest" else bad)
+            if case == "honest" or S > 2 * t + 1:
+                assert want["rc"] == 0 and GU.eq(want["cop"], honest["cop"])
+                summary = [0 if case == "honest" else 2, 0, 0xffffffff, 0]          # n_fallback, n_failed, first_failed, first_error
+            else:
+                assert want["rc"] == 8 and not want["cop"][bad].any()
+                summary = [2, 2, bad[0], 8]
+            laid = {nm: (np.ascontiguousarray(v[perm]) if nm != "w" else v) for nm, v in case_ins.items()}    # row s holds party perm[s]'s shares
+            tp = make_pipe(pkg, eng, n, t, N, k, m, laid, open_senders=S)
+            b = {nm: tp.buffer(nm)[0] for nm in (("w", "c") if with_w else ()) + ("a", "rbits", "rint", "rdash", "osh", "cop", "out", "status", "summary")}
+            got = {}
+            try:
+                for form, fused in (FORMS if S == 2 * t + 1 else FORMS[1:]):
+                    eng.set_fused_truncpr(fused)
+                    eng.h2d(b["cop"], np.zeros((N, 4), dtype=np.uint64))
+                    eng.h2d(b["out"], np.zeros((n, N, 4), dtype=np.uint64))
+                    assert eng.dev_truncpr_parties(list(ids), b["a"], b.get("w", 0), b["rbits"], b["rint"], k, m, N, n, t, b.get("c", 0), b["rdash"],
+                                                   b["osh"], b["cop"], b["out"], b["status"], b["summary"]) == 0
+                    got[form] = collect(eng, tp, with_w)
+                    tag = (case, form, n, t, S)
+                    assert GU.eq(got[form]["cop"], want["cop"]) and np.array_equal(got[form]["status"], want["status"]), tag
+                    assert got[form]["summary"].tolist() == summary, tag
+                    for nm in names:
+                        assert GU.eq(got[form][nm], want[nm][perm]), tag + (nm,)
+                if len(got) == 2:
+                    assert_same_bytes(got, (case, n, t, S))
+            finally:
+                tp.close()
+    finally:
+        eng.set_fused_truncpr(pkg.hbmpc.FUSED_TRUNCPR_DEFAULT)
 
 
 @pytest.mark.parametrize("seed", range(8))

@@ -16,6 +16,7 @@ from oracle import cref as O
 from tests import edge_inputs as X
 from tests import test_gpu_mul as M
 from tests import test_gpu_truncpr as T
+from tests.sender_sets import fpmul_expected, summary_tail
 from tests.test_gpu_mul import pkg_eng, pkg_gl  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -32,12 +33,6 @@ def arrays(F, case, n):
         else:
             out[nm] = None if v is None else F.arr(v)
     return out
-
-
-def summary_tail(status):
-    """n_failed, first_failed, first_error of a decode that left these status bytes (no OEC round: a failed chunk is 8)"""
-    bad = np.flatnonzero(status)
-    return [len(bad), int(bad[0]) if len(bad) else 0xffffffff, 8 if len(bad) else 0]
 
 
 # ---- Mul -------------------------------------------------------------------------------------------------------------------------
@@ -162,16 +157,6 @@ def test_truncpr_wide_moduli(pkg_eng, with_w):
 # ---- FpMul -----------------------------------------------------------------------------------------------------------------------
 FPMUL_FORMS = {"one": (1 << 20, NEVER), "four": (0, 0), "five": (0, NEVER)}      # hbmpc_set_fused_fpmul, hbmpc_set_fpmul_pair_decode
 FPMUL_NAMES = ("dop", "eop", "z", "rdash", "osh", "cop", "out")
-
-
-def fpmul_expected(ins, n, t, N, k, m):
-    """beaver_open_shares, batch_recover_p0, beaver_finalize, truncpr_rdash, the integer formula of truncpr.rs:275-297,
-    batch_recover_p0 again, truncpr_finalize"""
-    mul = M.expected(X.FR, ins, n, t, N, range(2 * t + 1))
-    tr = T.expected({"a": mul["out"], "w": None, "rbits": ins["rbits"], "rint": ins["rint"]}, n, t, N, k, m, 2 * t + 1)
-    return {"dop": mul["deop"][:N], "eop": mul["deop"][N:], "z": mul["out"], "rdash": tr["rdash"], "osh": tr["osh"], "cop": tr["cop"], "out": tr["out"],
-            "status": np.concatenate([tr["status"], mul["status"][N:]]),               # [0, N) the second open's, [N, 2 N) b - y of the first
-            "summary_first": summary_tail(mul["status"]), "summary": summary_tail(tr["status"])}
 
 
 def run_fpmul(pkg, eng, n, t, N, k, m, ins, forms_known=True):
