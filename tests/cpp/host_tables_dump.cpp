@@ -1,7 +1,11 @@
-// CPU-only dump of the host-side table builders (mpc-protocols_amd/csrc/tables.hpp, host_fr.hpp) for
-// tests/test_host_tables.py, which compares every value with the big-int oracle.  Built with
-// -fsanitize=address,undefined: the table code is the only host arithmetic in the product.
+// CPU-only dump of the host-side table builders for tests/test_host_tables.py, which compares every value with the big-int
+// oracle: the share tables (mpc-protocols_amd/csrc/tables.hpp, host_fr.hpp), the matrix-core tables (tables_mfma.hpp,
+// tables_mfma_gl.hpp), the square root's constants (tables_sqrt.hpp) and the RISS coefficients (tables_riss.hpp).  Built with
+// -fsanitize=address,undefined: together these are the host arithmetic of the product.
 //   usage: host_tables_dump <fr|gl> <n> <d> <t> <id0,id1,...> [full]
+//          host_tables_dump sqrt <fr-u29|fr-sat32|gl>          build_sqrt_table: a line "sqrt <layout numbers>", then the words
+//          host_tables_dump riss <fr|fr-sat32|gl> <n> <t> <own|-1>   build_riss_table: a line "riss <layout numbers>", then the words
+// (the words of these two modes follow their line as raw little-endian 32-bit values: the tables reach tens of megabytes)
 // full: the matrix-core tables are printed whatever their size, and so are the tables of the other instances -- enc (one row per point),
 // bflyR (point pairs, rows alpha^i 2^261: triple generation), bflyinv (point pairs of the inverse transform on a full domain)
 // (tests/test_mfma_inputs.py compares each byte for byte with the integer model of tests/mfma_model.py)
@@ -14,6 +18,8 @@
 #include "../../mpc-protocols_amd/csrc/tables.hpp"
 #include "../../mpc-protocols_amd/csrc/tables_mfma.hpp"
 #include "../../mpc-protocols_amd/csrc/tables_mfma_gl.hpp"
+#include "../../mpc-protocols_amd/csrc/tables_riss.hpp"
+#include "../../mpc-protocols_amd/csrc/tables_sqrt.hpp"
 
 using namespace hbmpc;
 
@@ -118,7 +124,50 @@ static int run(size_t n, size_t d, size_t t, const std::vector<size_t>& ids, boo
     }
     return 0;
 }
+static int impl_of(const char* name) {
+    if (std::strcmp(name, "gl") == 0) return IMPL_GOLD;
+    if (std::strcmp(name, "fr-sat32") == 0) return IMPL_SAT32;
+    if (std::strcmp(name, "fr-u29") == 0 || std::strcmp(name, "fr") == 0) return IMPL_U29;
+    return -1;
+}
+static HFr rdev_of(int impl) {  // the device Montgomery radix as a field value: 2^261 (u29) or 2^256 (sat32)
+    HFr two = HFr::from_u64(2), p = HFr::one();
+    for (int i = 0; i < (impl == IMPL_U29 ? 261 : 256); ++i) p = p * two;
+    return p;
+}
+static int put_raw(const std::vector<uint32_t>& w) {
+    std::fflush(stdout);
+    return std::fwrite(w.data(), 4, w.size(), stdout) == w.size() ? 0 : 4;
+}
+static int run_sqrt(int impl) {
+    SqrtLayout L;
+    std::vector<uint32_t> w;
+    if (impl == IMPL_GOLD) {
+        const uint64_t mod[4] = {HGl::P, 0, 0, 0};
+        w = build_sqrt_table<HGl>(mod, HGl::one(), impl, &L);
+    } else {
+        w = build_sqrt_table<HFr>(HFr::MOD, rdev_of(impl), impl, &L);
+    }
+    std::printf("sqrt %zu %zu %zu %zu %zu %zu %zu %zu %zu %d %d %d %d %d %zu\n", L.negw, L.posw, L.r2, L.one_p, L.half, L.half_p, L.e_sqrt, L.e_inv,
+                L.keyt, L.kbits, L.kshift, L.bits_sqrt, L.bits_inv, impl_nl(impl), w.size());
+    return put_raw(w);
+}
+static int run_riss(int impl, size_t n, size_t t, long own) {
+    RissLayout L;
+    const std::vector<uint32_t> w = impl == IMPL_GOLD ? build_riss_table<HGl>(n, t, own, impl, &L) : build_riss_table<HFr>(n, t, own, impl, &L);
+    if (w.size() != L.words) return 3;
+    std::printf("riss %zu %zu %zu %zu %zu %zu %d\n", L.coef, L.red, L.coef2, L.words, L.Tn, L.ncols, L.has2 ? 1 : 0);
+    return put_raw(w);
+}
 int main(int argc, char** argv) {
+    if (argc >= 3 && std::strcmp(argv[1], "sqrt") == 0) {
+        const int impl = impl_of(argv[2]);
+        return impl < 0 ? 1 : run_sqrt(impl);
+    }
+    if (argc >= 6 && std::strcmp(argv[1], "riss") == 0) {
+        const int impl = impl_of(argv[2]);
+        return impl < 0 ? 1 : run_riss(impl, std::strtoul(argv[3], nullptr, 10), std::strtoul(argv[4], nullptr, 10), std::strtol(argv[5], nullptr, 10));
+    }
     if (argc < 6) return 1;
     const size_t n = std::strtoul(argv[2], nullptr, 10), d = std::strtoul(argv[3], nullptr, 10), t = std::strtoul(argv[4], nullptr, 10);
     std::vector<size_t> ids;

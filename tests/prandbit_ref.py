@@ -196,17 +196,18 @@ def convert(p, n, t, r, parties=None, own=None):
     return out, out2
 
 
-_TABLES = {}
+_COLUMNS = {}
 
 
-def _tables(p, n, t):
-    key = (p, n, t)
-    if key not in _TABLES:
-        sets = tsets(n, t)
-        cp = [[0 if j in T else f_prime(p, n, T, j) for j in range(n)] for T in sets]
-        c2 = [[0 if j in T or n > 255 else f_gf(T, j) for j in range(n)] for T in sets]
-        _TABLES[key] = (cp, c2)
-    return _TABLES[key]
+def _tables(p, n, t, parties):
+    """({party: its column of f_T(alpha_j) over tsets(n, t)}, the same in GF(2^8)): a column is computed once, and only the parties asked for"""
+    sets = None
+    for j in set(parties):
+        if (p, n, t, j) not in _COLUMNS:
+            sets = sets or tsets(n, t)
+            _COLUMNS[(p, n, t, j)] = ([0 if j in T else f_prime(p, n, T, j) for T in sets],
+                                      [0 if j in T or n > 255 else f_gf(T, j) for T in sets])
+    return {j: _COLUMNS[(p, n, t, j)][0] for j in parties}, {j: _COLUMNS[(p, n, t, j)][1] for j in parties}
 
 
 def convert_fast(p, n, t, r, parties=None):
@@ -214,12 +215,12 @@ def convert_fast(p, n, t, r, parties=None):
     r = np.asarray(r, dtype=np.uint64)
     Tn, B = r.shape
     parties = list(range(n)) if parties is None else list(parties)
-    cp, c2 = _tables(p, n, t)
+    cp, c2 = _tables(p, n, t, parties)
     nl = (p.bit_length() + 15) // 16
     C = np.zeros((Tn, len(parties) * nl), dtype=np.float64)
     for k in range(Tn):
         for q, j in enumerate(parties):
-            v = cp[k][j]
+            v = cp[j][k]
             for b in range(nl):
                 C[k, q * nl + b] = (v >> (16 * b)) & 0xFFFF
     assert Tn * 65535 * 65535 < 2**53
@@ -239,7 +240,7 @@ def convert_fast(p, n, t, r, parties=None):
     par = (r & np.uint64(1)).astype(np.float64)  # [Tn][B]
     out2 = []
     for j in parties:
-        planes = np.array([[(c2[k][j] >> b) & 1 for b in range(8)] for k in range(Tn)], dtype=np.float64)  # [Tn][8]
+        planes = np.array([[(c2[j][k] >> b) & 1 for b in range(8)] for k in range(Tn)], dtype=np.float64)  # [Tn][8]
         bits = (par.T @ planes).astype(np.int64) & 1  # [B][8]
         out2.append([int(sum(int(bits[i, b]) << b for b in range(8))) for i in range(B)])
     return out, out2

@@ -164,6 +164,32 @@ def test_convert_one_party_form(pkg, field, impl, gf2):
 
 
 @pytest.mark.parametrize("field,impl", CONFIGS)
+def test_convert_many_parties(pkg, field, impl):
+    """up to the supported range (255 parties in GF(2^8), 256 without it, 8128 sets): every form, with and without the GF(2^8) output,
+    against the restatement on all columns for the first, the last and a middle party, and the all-parties call on the same rows"""
+    eng = engine(pkg, field, impl)
+    try:
+        B = 65
+        for n, t in ((128, 2), (37, 3), (17, 5), (255, 1), (256, 1)):
+            Tn = math.comb(n, t)
+            assert Tn <= PR.MAX_TSETS
+            ids = [0, 1, n // 2, n - 2, n - 1]
+            r = riss_values(n, Tn, B, seed=n + t)
+            assert (r[:, 2] == max_r(n)).all()
+            want, want2 = PR.convert_fast(PR.PRIME[field], n, t, r, parties=ids)
+            rc, full, full2 = dev_convert(eng, r, n, t, gf2=n <= 255)
+            assert rc == 0, eng.last_error()
+            for gf2 in ((True, False) if n <= 255 else (False,)):
+                for form in (0, 1, 2):
+                    rc, out, out2 = dev_convert(eng, r, n, t, party_ids=ids, gf2=gf2, form=form)
+                    assert rc == 0, (eng.last_error(), n, t, gf2, form)
+                    check(field, out, out2, want, want2, np.arange(B))
+                    assert np.array_equal(out, full[ids]) and (not gf2 or np.array_equal(out2, full2[ids])), (n, t, gf2, form)
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("field,impl", CONFIGS)
 def test_convert_host_pointer_form(pkg, field, impl):
     eng = engine(pkg, field, impl)
     try:
@@ -329,10 +355,7 @@ def test_error_codes(pkg):
                 assert eng.dev_riss_fold(buf, 16, 4, 4, 57, buf + 65536, buf + 131072) == 0
                 assert eng.dev_riss_fold(buf, 5, 4, 4, 59, buf + 65536, buf + 131072) == PR.FIELD_CAPACITY
             fr.sync(), gl.sync()
-            # n = 256 without the byte output is a supported shape
-            fr.h2d(buf, np.zeros(256 * 4, dtype=np.uint64))
-            assert fr.dev_riss_convert_parties(buf, 256, 1, 4, buf + 65536, 0) == 0, fr.last_error()
-            fr.sync()
+            # n = 256 without the byte output is a supported shape: test_convert_many_parties compares its values
             # the wrong field's entry points: TypeMismatch
             import ctypes as C
             args = (C.c_void_p(buf), C.c_size_t(7), C.c_size_t(2), C.c_size_t(4), None, C.c_size_t(7), C.c_int(0), C.c_void_p(buf), None, None)
