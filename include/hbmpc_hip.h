@@ -249,6 +249,22 @@ ShareErrorCode hbmpc_pipe_preprocessing_create(hbmpc_ctx* ctx, size_t n, size_t 
  * / HBMPC_NO_SQUARE_ROOT from the finalize's summary -- where the reference's `?` returns; it synchronises once, after the whole
  * call, so a checked run that fails has run the later steps too.  Y and Z are workspaces: unspecified after a run. */
 ShareErrorCode hbmpc_pipe_randbit_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream, hbmpc_pipe** pipe_out);
+/* PRandBit (B bits, a multiple of t + 1) and PRandInt (any B) for all n parties (fpmul/prandbitd.rs; honeybadger/mod.rs:1951-2150):
+ * handles over hbmpc_dev_prandbit_parties / hbmpc_dev_prandint_parties (below), which is what run() calls -- one launch for a small
+ * batch, the separate launches otherwise.  PRandBit spans two fields: ctx_fr is a bls12-381 Fr context, ctx_gl a Goldilocks one on
+ * the same device (a context of the wrong field: TypeMismatch); open_senders = 0 means 2t + 1.  create runs the device call's own
+ * checks (shape, capacity rule, contexts on one device) and answers with its code; *pipe_out is NULL after every refusal.  stream
+ * NULL: the handle creates a stream of its own (the two contexts' own streams differ) and destroys it with the handle.  Every buffer has an element type of its own, which hbmpc_pipe_buffer's elements_out and
+ * hbmpc_pipe_upload / _download count in:
+ *   inputs   contrib ([n][C(n,t)][B] u64), b_q ([n][B] u64; PRandBit)
+ *   outputs  sums ([C(n,t)][B] u64), bad ([n][C(n,t)] bytes), r_p ([n][B] U256); PRandBit also r_2 ([n][B] bytes), r_q, rb ([n][B] u64),
+ *            opened ([B] u64), b_p ([n][B] U256), b_2 ([n][B] bytes), rstatus ([n G] bytes), summary_first, summary (16 bytes each)
+ *   workspaces (PRandBit)  Y ([n][n][G] u64), Z ([n][G] u64): unspecified after a run
+ * hbmpc_pipe_summary reads summary (PRandBit).  Checked mode returns the first failing decode's error.  capture() / replay() as for the
+ * other handles (capture mode is per thread, so it covers both contexts). */
+ShareErrorCode hbmpc_pipe_prandbit_create(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl, size_t n, size_t t, size_t B, size_t lk_bits, size_t open_senders,
+                                          void* stream, hbmpc_pipe** pipe_out);
+ShareErrorCode hbmpc_pipe_prandint_create(hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t B, size_t lk_bits, void* stream, hbmpc_pipe** pipe_out);
 void hbmpc_pipe_destroy(hbmpc_pipe* pipe);
 ShareErrorCode hbmpc_pipe_part(hbmpc_pipe* pipe, const char* name, hbmpc_pipe** part_out);
 ShareErrorCode hbmpc_pipe_buffer(hbmpc_pipe* pipe, const char* name, void** dev_out, size_t* elements_out);
@@ -966,6 +982,34 @@ ShareErrorCode hbmpc_dev_prandbit_finalize_parties(hbmpc_ctx* ctx, const uint64_
                                                    size_t parties, U256* bp_out, uint8_t* b2_out, void* stream);
 ShareErrorCode hbmpc_prandbit_finalize_parties(hbmpc_ctx* ctx, const uint64_t* opened, const U256* r_p, const uint8_t* r_2, size_t B,
                                                size_t parties, U256* bp_out, uint8_t* b2_out);
+/* PRandBit for all n parties of this device in ONE call, from an Fr context and a Goldilocks context on the same device
+ * (prandbitd.rs:638-647, 667-684, 311-356, 437-446, 189-211; driven by honeybadger/mod.rs:1951-2150).  G = B / (t + 1) chunks.
+ *   contrib [n][C(n,t)][B] the senders' values, b_q [n][B] the Goldilocks shares of the bits
+ *   -> sums [C(n,t)][B], bad [n][C(n,t)] verdict bytes (hbmpc_dev_riss_fold), r_p [n][B] Fr, r_2 [n][B] GF(2^8), r_q [n][B] Goldilocks,
+ *      rb = r_q + b_q, opened [B] (BatchRecon of degree t in chunks of t + 1 from senders 0 .. open_senders - 1), b_p [n][B] Fr and
+ *      b_2 [n][B] bytes (try_finalize_bit), rstatus [n G] as the two decodes of the open leave it, summary_first / summary (nullable)
+ *      the summaries of the recipients' decodes and of the revealed values' decode.  y_ws [n][n][G], z_ws [n][G]: workspaces,
+ *      unspecified afterwards.
+ * open_senders = 0 means 2t + 1: no OEC round, a failed chunk is final and opens to zero (BatchRecon acts as soon as d + t + 1 values
+ * have arrived); up to n takes the decodes' OEC path.  stream NULL: the Fr context's own; the Goldilocks context's work runs on it too.
+ * With at most hbmpc_set_fused_prandbit chunks, a U29 Fr context, single-launch decodes on, 1 <= t, 3t + 1 <= n <= 16,
+ * open_senders = 2t + 1 and coefficient tables that fit a workgroup's LDS ((4,1) .. (12,3)) the call is ONE launch, a workgroup per
+ * chunk (csrc/kernels_prandbit_wg.hpp, csrc/prandbit_route.hpp); otherwise hbmpc_dev_riss_fold, the two hbmpc_[gl_]dev_riss_convert_parties,
+ * the add, the encode, the two decodes and hbmpc_dev_prandbit_finalize_parties.  Same bytes either way.
+ * Everything is checked before the first launch: B % (t + 1) != 0, n < 3t + 1 or beyond the shapes of the conversion, n > 255, null
+ * buffers or contexts, contexts on different devices -> InvalidInput; the fold's capacity rule -> HBMPC_FIELD_CAPACITY; a context of
+ * the wrong field -> TypeMismatch; B = 0 -> ShareSuccess with nothing written. */
+ShareErrorCode hbmpc_dev_prandbit_parties(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl, const uint64_t* contrib, const uint64_t* b_q, size_t n, size_t t,
+                                          size_t B, size_t lk_bits, size_t open_senders, uint64_t* sums, uint8_t* bad, U256* r_p, uint8_t* r_2,
+                                          uint64_t* r_q, uint64_t* rb, uint64_t* y_ws, uint64_t* z_ws, uint64_t* opened, U256* b_p, uint8_t* b_2,
+                                          uint8_t* rstatus, hbmpc_recover_summary* summary_first, hbmpc_recover_summary* summary, void* stream);
+/* PRandInt the same way (any B): the fold and the conversion over Fr -> sums, bad, r_p.  One launch under the same rule (a workgroup
+ * takes up to t + 1 elements), otherwise hbmpc_dev_riss_fold and hbmpc_dev_riss_convert_parties. */
+ShareErrorCode hbmpc_dev_prandint_parties(hbmpc_ctx* ctx_fr, const uint64_t* contrib, size_t n, size_t t, size_t B, size_t lk_bits, uint64_t* sums,
+                                          uint8_t* bad, U256* r_p, void* stream);
+/* hbmpc_dev_prandbit_parties / hbmpc_dev_prandint_parties run as one launch up to max_chunks chunks of t + 1 elements (0: always the
+ * separate launches); read from the Fr context.  Same bytes either way (A/B aid). */
+ShareErrorCode hbmpc_set_fused_prandbit(hbmpc_ctx* ctx_fr, size_t max_chunks);
 /* A/B aid: how the conversion lays its work out.  0 = by size (default), 1 = always a workgroup per 64 elements and 16 parties,
  * 2 = always a workgroup per 64 elements and party with the sets in four slices.  Same results. */
 ShareErrorCode hbmpc_set_riss_form(hbmpc_ctx* ctx, int form);

@@ -17,6 +17,10 @@
 //   RanDouSha      DouShaNode deal + RanDouShaNode: both Vandermonde products, verifier interpolations + tests, output slice
 //                  double_share/double_share_generation.rs:151-215, ran_dou_sha/mod.rs:371-449,569-602,314-331
 //   Preprocessing  run_preprocessing's triple part (honeybadger/mod.rs:1239-1393): RanSha -> a, b; RanDouSha -> r; TripleGen
+//   PRandIntPipe   fold of the RISS contributions, conversion to Fr shares      fpmul/prandbitd.rs:667-684,311-356
+//   PRandBitPipe   ... and to Goldilocks and GF(2^8), open r + b, finalize      fpmul/prandbitd.rs:311-356,437-446,189-211
+//                  (handles of csrc/capi_pipelines_riss.hip over an Fr and a Goldilocks context; PRandInt / PRandBit below are the
+//                  compositions of eight device calls with the prepare() / finish() seam)
 //
 // run() only ENQUEUES on the stream; capture() records the same call sequence into a HIP graph after two eager runs and
 // replay() launches it -- at the batch sizes the protocols really use that removes the launch overhead that dominates.
@@ -372,6 +376,65 @@ class PRandBit : public PRandInt {
   private:
     hbmpc_ctx* gl_;
     std::vector<size_t> ids_;
+};
+
+// The same two as hbmpc_pipe handles (csrc/capi_pipelines_riss.hip): run() is ONE device call (hbmpc_dev_prandint_parties /
+// hbmpc_dev_prandbit_parties: one launch for a small batch), capture() / replay() work as for the other handles.  Every buffer has an
+// element type of its own, which the typed accessors below count in.
+class RissPipeline : public Pipeline {
+  public:
+    template <class T>
+    T* typed(const char* name, size_t* elements = nullptr) const {
+        return reinterpret_cast<T*>(buffer(name, elements));
+    }
+    template <class T>
+    void upload_typed(const char* name, const T* src, size_t elements) { pl_check(hbmpc_pipe_upload(h_, name, src, elements), ctx_, name); }
+    template <class T>
+    void download_typed(const char* name, T* dst, size_t elements) { pl_check(hbmpc_pipe_download(h_, name, dst, elements), ctx_, name); }
+
+  protected:
+    using Pipeline::Pipeline;
+};
+
+// contrib [n][C(n,t)][B] -> sums [C(n,t)][B], bad [n][C(n,t)] bytes, r_p [n][B] (prandbitd.rs:667-684, 311-356).  Any B.
+class PRandIntPipe : public RissPipeline {
+  public:
+    PRandIntPipe(hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t B, size_t lk_bits, void* stream)
+        : RissPipeline(ctx_fr, create(ctx_fr, n, t, B, lk_bits, stream), stream) {
+        contrib = typed<uint64_t>("contrib"), sums = typed<uint64_t>("sums"), bad = typed<uint8_t>("bad"), r_p = typed<U256>("r_p");
+    }
+    uint64_t *contrib, *sums;
+    uint8_t* bad;
+    U256* r_p;
+
+  private:
+    static hbmpc_pipe* create(hbmpc_ctx* ctx, size_t n, size_t t, size_t B, size_t lk_bits, void* stream) {
+        hbmpc_pipe* h = nullptr;
+        pl_check(hbmpc_pipe_prandint_create(ctx, n, t, B, lk_bits, stream, &h), ctx, "hbmpc_pipe_prandint_create");
+        return h;
+    }
+};
+
+// ... and b_q [n][B] -> r_2, r_q, rb, opened [B], b_p [n][B] Fr, b_2 [n][B] bytes (prandbitd.rs:437-446, 189-211).  B a multiple of
+// t + 1; open_senders: 0 = the reference's 2t + 1 (no OEC round).  last_summary() is the revealed values' decode's.
+class PRandBitPipe : public RissPipeline {
+  public:
+    PRandBitPipe(hbmpc_ctx* ctx_gl, hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t B, size_t lk_bits, void* stream, size_t open_senders = 0)
+        : RissPipeline(ctx_gl, create(ctx_fr, ctx_gl, n, t, B, lk_bits, open_senders, stream), stream) {
+        contrib = typed<uint64_t>("contrib"), b_q = typed<uint64_t>("b_q"), sums = typed<uint64_t>("sums"), r_q = typed<uint64_t>("r_q");
+        rb = typed<uint64_t>("rb"), opened = typed<uint64_t>("opened"), bad = typed<uint8_t>("bad"), r_2 = typed<uint8_t>("r_2");
+        b_2 = typed<uint8_t>("b_2"), rstatus = typed<uint8_t>("rstatus"), r_p = typed<U256>("r_p"), b_p = typed<U256>("b_p");
+    }
+    uint64_t *contrib, *b_q, *sums, *r_q, *rb, *opened;
+    uint8_t *bad, *r_2, *b_2, *rstatus;
+    U256 *r_p, *b_p;
+
+  private:
+    static hbmpc_pipe* create(hbmpc_ctx* fr, hbmpc_ctx* gl, size_t n, size_t t, size_t B, size_t lk_bits, size_t open_senders, void* stream) {
+        hbmpc_pipe* h = nullptr;
+        pl_check(hbmpc_pipe_prandbit_create(fr, gl, n, t, B, lk_bits, open_senders, stream, &h), fr, "hbmpc_pipe_prandbit_create");
+        return h;
+    }
 };
 
 }  // namespace hbmpc

@@ -23,6 +23,7 @@
 #include "kernels_mul_wave.hpp"
 #include "kernels_triplegen_wg.hpp"
 #include "kernels_randbit_wg.hpp"
+#include "kernels_prandbit_wg.hpp"
 #include "launchers.hpp"
 #include "tables.hpp"
 #include "tables_mfma.hpp"
@@ -32,6 +33,7 @@
 #include "encode_route.hpp"
 #include "recover_route.hpp"
 #include "protocol_route.hpp"
+#include "prandbit_route.hpp"
 #include "tables_sqrt.hpp"
 #include "tables_riss.hpp"
 
@@ -41,6 +43,10 @@ using namespace hbmpc;
 // largest swept size at which one launch measured ahead of or level with the nine, eager and replayed, at n = 16 and at n = 4
 // (profiles/fused_randbit_sweep.txt; over Fr each element's 255-bit exponentiation runs on a single lane in either form)
 constexpr size_t FUSED_RANDBIT_FR = 256, FUSED_RANDBIT_GL = 1024;
+// hbmpc_dev_prandbit_parties / hbmpc_dev_prandint_parties as one launch: the default of hbmpc_set_fused_prandbit, in chunks of t + 1
+// elements -- the largest swept count at which one launch was not slower than the composition of eight calls at (7,2) and at (10,3)
+// (profiles/fused_prandbit_sweep.txt)
+constexpr size_t FUSED_PRANDBIT = 256;
 constexpr size_t STAGE_PIN_BLOCK = (size_t)2048 << 10;  // pinned host block of the small-call staging path (Stage, hbmpc_scrub_staging)
 struct hbmpc_ctx {
     int device = 0;
@@ -81,6 +87,7 @@ struct hbmpc_ctx {
     size_t fused_truncpr_max = 768;                // hbmpc_dev_truncpr_parties: the same (profiles/fused_truncpr_sweep.txt: ahead or level, eager and replayed)
     size_t fused_mul_max = 1024;                   // hbmpc_dev_mul_parties: the same (profiles/fused_mul_sweep.txt: ahead both eager and replayed)
     size_t fused_randbit_max = FUSED_RANDBIT_FR;   // hbmpc_dev_randbit_parties: one launch (a workgroup per chunk of t + 1 elements) up to this many chunks (0: never); per field, hbmpc_create
+    size_t fused_prandbit_max = FUSED_PRANDBIT;    // hbmpc_dev_prandbit_parties / _prandint_parties (read from the Fr context): the same, in chunks of t + 1 elements
     bool gather_row_copies = false;                // hbmpc_dev_gather_party_major: take the per-row peer copies even where the 2-D copy applies (A/B aid)
     bool list_rows_in_kernel = true;               // the producers' mixing step writes the parties' lists itself (k_mfma_bfly<.., LISTS>)
     bool mfma_bfly = true;                         // large encodes take the domain points in pairs (kernels_mfma_bfly.hpp)
@@ -445,6 +452,7 @@ KNOB_SETTER(hbmpc_set_fused_truncpr, fused_truncpr_max)
 KNOB_SETTER(hbmpc_set_fused_triplegen, fused_triplegen_max)
 KNOB_SETTER(hbmpc_set_fused_mul, fused_mul_max)
 KNOB_SETTER(hbmpc_set_fused_randbit, fused_randbit_max)
+KNOB_SETTER(hbmpc_set_fused_prandbit, fused_prandbit_max)
 KNOB_SETTER(hbmpc_set_fpmul_pair_decode, pair_decode_min)
 #undef KNOB_SETTER
 extern "C" ShareErrorCode hbmpc_set_gather_row_copies(hbmpc_ctx* ctx, int on) {  // either field
@@ -2270,3 +2278,4 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
 #include "capi_truncpr.inc"
 #include "capi_mul.inc"
 #include "capi_randbit.inc"
+#include "capi_prandbit.inc"

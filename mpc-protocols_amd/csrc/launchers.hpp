@@ -211,5 +211,10 @@ void launch_riss_convert(int impl, bool wide, const uint64_t* r, size_t B, unsig
                          uint32_t* out, uint8_t* out2, hipStream_t s);
 void launch_prandbit_finalize(int impl, const uint64_t* v, const uint32_t* r_p, const uint8_t* r_2, size_t N, unsigned parties, uint32_t* bp,
                               uint8_t* b2, hipStream_t s);  // Fr only
+// PRandBit (bit) / PRandInt for all parties, a workgroup per chunk of t + 1 elements (kernels_prandbit_wg.hpp): the Fr side over U29
+// only (Goldilocks is the second field inside the same kernel).
+// false: the layout does not fit a workgroup's LDS or the LDS attribute could not be set; dry_run: only say which
+struct PRandBitWgArgs;
+bool launch_prandbit_wg(bool bit, const PRandBitWgArgs& a, int device, hipStream_t s, bool dry_run);
 
 }  // namespace hbmpc

@@ -77,6 +77,7 @@ def riss_tsets(n, t):
 FUSED_TRUNCPR_DEFAULT = 768  # hbmpc_set_fused_truncpr's default (csrc/hbmpc_capi.hip)
 FUSED_MUL_DEFAULT = 1024  # hbmpc_set_fused_mul's default (csrc/hbmpc_capi.hip)
 FUSED_RANDBIT_DEFAULT = {"fr": 256, "goldilocks": 1024}  # hbmpc_set_fused_randbit's default per field (FUSED_RANDBIT_FR / _GL, csrc/hbmpc_capi.hip)
+FUSED_PRANDBIT_DEFAULT = 256  # hbmpc_set_fused_prandbit's default (FUSED_PRANDBIT, csrc/hbmpc_capi.hip)
 
 
 def fixed_point_reciprocal_scaled(denom, f):
@@ -662,6 +663,26 @@ class Engine:
         bp, b2 = u256((parties, B)), np.zeros((parties, B), dtype=np.uint8)
         rc = self.L.hbmpc_prandbit_finalize_parties(self.ctx, _p(opened), _p(r_p), _p(r_2), C.c_size_t(B), C.c_size_t(parties), _p(bp), _p(b2))
         return rc, bp, b2
+
+    def prandbit_parties(self, eng_gl, contrib_d, bq_d, n, t, B, lk_bits, sums_d, bad_d, rp_d, r2_d, rq_d, rb_d, y_d, z_d, opened_d, bp_d, b2_d,
+                         rstatus_d, summary_first_d=0, summary_d=0, open_senders=0, stream=0):
+        """PRandBit for all n parties in one call (hbmpc_dev_prandbit_parties; device pointers), on this Fr engine and the Goldilocks
+        engine eng_gl of the same device: one launch up to hbmpc_set_fused_prandbit chunks of t + 1 elements for the shapes whose
+        tables fit a workgroup's LDS, the eight separate launches otherwise; returns the ShareErrorCode"""
+        return self.L.hbmpc_dev_prandbit_parties(self.ctx, eng_gl.ctx if eng_gl is not None else None, C.c_void_p(contrib_d), C.c_void_p(bq_d),
+                                                 *(C.c_size_t(v) for v in (n, t, B, lk_bits, open_senders)),
+                                                 *(C.c_void_p(p) for p in (sums_d, bad_d, rp_d, r2_d, rq_d, rb_d, y_d, z_d, opened_d, bp_d, b2_d,
+                                                                           rstatus_d, summary_first_d, summary_d)), C.c_void_p(stream))
+
+    def prandint_parties(self, contrib_d, n, t, B, lk_bits, sums_d, bad_d, rp_d, stream=0):
+        """PRandInt for all n parties in one call (hbmpc_dev_prandint_parties; device pointers); returns the ShareErrorCode"""
+        return self.L.hbmpc_dev_prandint_parties(self.ctx, C.c_void_p(contrib_d), *(C.c_size_t(v) for v in (n, t, B, lk_bits)),
+                                                 *(C.c_void_p(p) for p in (sums_d, bad_d, rp_d)), C.c_void_p(stream))
+
+    def set_fused_prandbit(self, max_chunks: int):
+        """hbmpc_dev_prandbit_parties / _prandint_parties are one launch up to this many chunks of t + 1 elements (0: always the
+        separate launches); read from the Fr engine"""
+        assert self.L.hbmpc_set_fused_prandbit(self.ctx, C.c_size_t(max_chunks)) == 0
 
     def set_riss_form(self, form: int):
         """A/B aid: 0 by size, 1 a workgroup per 16 parties, 2 a workgroup per party with the sets in slices"""

@@ -19,7 +19,10 @@ in the library; this file only names things for the tests and bench.py.
   RandBit        RandBit: Beaver square of a, BatchRecon of a^2, phase 2   fpmul/rand_bit.rs:242-293,197-220
   PRandInt       fold of the RISS contributions, conversion to Fr shares   fpmul/prandbitd.rs:667-684,311-356
   PRandBit       ... and to Goldilocks and GF(2^8), open r + b, finalize   fpmul/prandbitd.rs:311-356,437-446,189-211
-PRandInt and PRandBit span two fields, so they are compositions of device calls here, not hbmpc_pipe handles.
+  PRandIntPipe / PRandBitPipe  the same two over the hbmpc_pipe_prandint / _prandbit handles: run() is ONE device call
+                 (hbmpc_dev_prandint_parties / hbmpc_dev_prandbit_parties), one launch for a small batch
+PRandInt and PRandBit are the compositions of eight device calls over two contexts (their prepare() / finish() seam lets a test stand
+between the parties' messages and the open); PRandIntPipe and PRandBitPipe are the handles (csrc/capi_pipelines_riss.hip).
 """
 from __future__ import annotations
 
@@ -342,6 +345,64 @@ class RandBit(_Pipe):
         """(first, n_failed) of the finalize"""
         b = self.bytes_of("summary", 16)
         return int(b[:8].view(np.uint64)[0]), int(b[8:12].view(np.uint32)[0])
+
+
+class _RissPipe(_Pipe):
+    """What the PRandBit / PRandInt handles share: every buffer has an element type of its own (u64, U256 or bytes), and
+    hbmpc_pipe_upload / _download count elements of that type."""
+    _EB = {"contrib": 8, "b_q": 8, "sums": 8, "bad": 1, "r_p": 32, "r_2": 1, "r_q": 8, "rb": 8, "Y": 8, "Z": 8, "opened": 8, "b_p": 32, "b_2": 1,
+           "rstatus": 1, "summary_first": 1, "summary": 1}
+
+    def upload_named(self, name, arr):
+        arr = np.ascontiguousarray(arr)
+        self._rc(self.eng.L.hbmpc_pipe_upload(self.h, name.encode(), arr.ctypes.data_as(C.c_void_p), C.c_size_t(arr.nbytes // self._EB[name])),
+                 f"upload {name!r}")
+
+    def download_named(self, name, shape=None):
+        """the whole buffer (shape: of the result; default flat): uint64 ([..., 4] for the U256 buffers) or uint8"""
+        eb, count = self._EB[name], self.buffer(name)[1]
+        out = np.zeros((count, 4) if eb == 32 else (count,), dtype=np.uint8 if eb == 1 else np.uint64)
+        self._rc(self.eng.L.hbmpc_pipe_download(self.h, name.encode(), out.ctypes.data_as(C.c_void_p), C.c_size_t(count)), f"download {name!r}")
+        return out if shape is None else out.reshape(shape)
+
+
+class PRandIntPipe(_RissPipe):
+    """PRandInt for all n parties as one handle (hbmpc_pipe_prandint_create; prandbitd.rs:667-684, 311-356): contrib [n][C(n,t)][B] u64
+    -> sums [C(n,t)][B], bad [n][C(n,t)] verdict bytes, r_p [n][B] the Fr shares.  Any B.  run() is one library call
+    (hbmpc_dev_prandint_parties): ONE launch up to hbmpc_set_fused_prandbit chunks of t + 1 elements for the shapes whose tables fit a
+    workgroup's LDS, two launches otherwise."""
+
+    def __init__(self, eng_fr, n, t, B, lk_bits, stream=0):
+        self.n, self.t, self.B, self.lk_bits = n, t, B, lk_bits
+        h = C.c_void_p()
+        rc = eng_fr.L.hbmpc_pipe_prandint_create(eng_fr.ctx, *[C.c_size_t(v) for v in (n, t, B, lk_bits)], C.c_void_p(stream), C.byref(h))
+        if rc != 0:
+            raise RuntimeError(f"hbmpc_pipe_prandint_create{(n, t, B, lk_bits)} -> ShareErrorCode {rc}: {eng_fr.last_error()}")
+        super().__init__(eng_fr, h, stream)
+
+
+class PRandBitPipe(_RissPipe):
+    """PRandBit for all n parties as one handle (hbmpc_pipe_prandbit_create; prandbitd.rs:667-684, 311-356, 437-446, 189-211), from an Fr
+    engine and a Goldilocks engine on the same device.  Inputs contrib [n][C(n,t)][B] u64, b_q [n][B]; outputs sums, bad, r_p, r_2, r_q, rb,
+    opened [B], b_p [n][B] Fr, b_2 [n][B] bytes, rstatus, summary_first, summary.  B a multiple of t + 1.  open_senders: how many parties'
+    messages the open decodes from; default 2t + 1 (no OEC round: BatchRecon acts as soon as d + t + 1 values have arrived).  run() is one
+    library call (hbmpc_dev_prandbit_parties): ONE launch up to hbmpc_set_fused_prandbit chunks when the open has exactly 2t + 1 senders
+    and the tables fit a workgroup's LDS ((4,1) .. (12,3)), eight launches otherwise."""
+
+    def __init__(self, eng_gl, eng_fr, n, t, B, lk_bits, stream=0, open_senders=None):
+        self.n, self.t, self.B, self.lk_bits, self.G = n, t, B, lk_bits, B // (t + 1)
+        self.open_senders = 2 * t + 1 if open_senders is None else open_senders
+        self.fr = eng_fr
+        h = C.c_void_p()
+        rc = eng_fr.L.hbmpc_pipe_prandbit_create(eng_fr.ctx, eng_gl.ctx, *[C.c_size_t(v) for v in (n, t, B, lk_bits, self.open_senders)],
+                                                 C.c_void_p(stream), C.byref(h))
+        if rc != 0:
+            raise RuntimeError(f"hbmpc_pipe_prandbit_create{(n, t, B, lk_bits, self.open_senders)} -> ShareErrorCode {rc}: {eng_fr.last_error()}")
+        super().__init__(eng_gl, h, stream)  # the handle's own context is the Goldilocks one (the open's decode counters are its)
+
+    def open_summary(self):
+        """(n_fallback, n_failed, first_failed, first_error) of the two decodes of the open"""
+        return [tuple(int(v) for v in self.download_named(k).view(np.uint32)) for k in ("summary_first", "summary")]
 
 
 class _Riss:

@@ -368,6 +368,22 @@ impl GpuShares {
         let rc = unsafe { sys::hbmpc_pipe_randbit_create(self.ctx, n, t, bits, stream, &mut p) };
         self.wrap(rc, p, n)
     }
+    /// PRandBit for all n parties (fpmul/prandbitd.rs:638-647,667-684,311-356,437-446,189-211; honeybadger/mod.rs:1951-2150): `self` is the
+    /// bls12-381 Fr context, `gl` a Goldilocks context on the same device; `bits` a multiple of t + 1 (prandbitd.rs:472-476).  Buffers
+    /// contrib, b_q (inputs, `upload_u64`), sums, r_q, rb, opened (`download_u64`), r_p, b_p (`download`), bad, r_2, b_2, rstatus
+    /// (`download_bytes`).  One device call per run: one launch for a small batch
+    pub fn pipe_prandbit<'a>(&'a self, gl: &'a GpuShares, n: usize, t: usize, bits: usize, l_plus_k: usize,
+                             stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'a>, InterpolateError> {
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_prandbit_create(self.ctx, gl.ctx, n, t, bits, l_plus_k, 0, stream, &mut p) };
+        self.wrap(rc, p, n)
+    }
+    /// PRandInt for all n parties (prandbitd.rs:667-684,311-356): any batch; buffers contrib (input), sums, bad, r_p
+    pub fn pipe_prandint(&self, n: usize, t: usize, batch: usize, l_plus_k: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_prandint_create(self.ctx, n, t, batch, l_plus_k, stream, &mut p) };
+        self.wrap(rc, p, n)
+    }
 }
 
 impl<'a> GpuPipeline<'a> {
@@ -400,6 +416,26 @@ impl<'a> GpuPipeline<'a> {
         let rc = unsafe { sys::hbmpc_pipe_download(self.pipe, Self::name(name).as_ptr(), v.as_mut_ptr() as *mut core::ffi::c_void, elements) };
         self.gpu.check(rc, 0)?;
         Ok(v.iter().map(from_u256).collect())
+    }
+    /// the PRandBit / PRandInt handles' buffers have element types of their own: `u64` values (contrib, b_q, sums, r_q, rb, opened) ...
+    pub fn upload_u64(&self, name: &str, values: &[u64]) -> Result<(), InterpolateError> {
+        let rc = unsafe { sys::hbmpc_pipe_upload(self.pipe, Self::name(name).as_ptr(), values.as_ptr() as *const core::ffi::c_void, values.len()) };
+        self.gpu.check(rc, 0)?;
+        let rc = unsafe { sys::hbmpc_pipe_sync(self.pipe) };  // the copy reads `values`
+        self.gpu.check(rc, 0)
+    }
+    pub fn download_u64(&self, name: &str, elements: usize) -> Result<Vec<u64>, InterpolateError> {
+        let mut v = vec![0u64; elements];
+        let rc = unsafe { sys::hbmpc_pipe_download(self.pipe, Self::name(name).as_ptr(), v.as_mut_ptr() as *mut core::ffi::c_void, elements) };
+        self.gpu.check(rc, 0)?;
+        Ok(v)
+    }
+    /// ... and bytes (bad, r_2, b_2, rstatus)
+    pub fn download_bytes(&self, name: &str, elements: usize) -> Result<Vec<u8>, InterpolateError> {
+        let mut v = vec![0u8; elements];
+        let rc = unsafe { sys::hbmpc_pipe_download(self.pipe, Self::name(name).as_ptr(), v.as_mut_ptr() as *mut core::ffi::c_void, elements) };
+        self.gpu.check(rc, 0)?;
+        Ok(v)
     }
     /// enqueue the whole pipeline on its stream
     pub fn run(&self) -> Result<(), InterpolateError> {

@@ -7,7 +7,9 @@ kernel's bytes and its floors:
                                         the register-resident modmul hbmpc_dev_modmul_ubench measures is 203 (fr_u29.hpp)
 At n = 16, t = 5 and B = 384, 4 096 the one-party conversion is also spelled with what the library had before -- one
 hbmpc_dev_fr_op_scalar (multiply by f_T(alpha_j)) and one hbmpc_dev_fr_op (add) per set, r_T widened to U256 -- and timed in the same
-process: `baseline_one_party_ms` and `speedup_one_party`.
+process: `baseline_one_party_ms` and `speedup_one_party`.  Where B is a multiple of t + 1 the whole protocol as one device call
+(hbmpc_dev_prandbit_parties) is timed too, with the one-launch threshold at 2^30 and at 0: `parties_call_one_ms`,
+`parties_call_launches_ms`, and `parties_call_form` (which form the first ran as; tools/sweep_fused_prandbit.py sweeps the small batches).
     python tools/bench_prandbit.py [--shapes 16:5:384,16:5:4096,16:5:16384,4:1:1048576] [--iters 10] [--no-baseline]"""
 import argparse
 import json
@@ -101,6 +103,28 @@ def main():
         row["convert_fr_one_party_ms"] = timed(lambda: fr.dev_riss_convert_parties(O, n, t, B, P, 0, party_ids=[j], own_sets_only=True, stream=st))
         row["convert_gl_one_party_ms"] = timed(lambda: gl.dev_riss_convert_parties(O, n, t, B, Q, 0, party_ids=[j], own_sets_only=True, stream=st))
         row["finalize_ms"] = timed(lambda: fr.dev_prandbit_finalize_parties(opened.data_ptr(), P, R2, B, n, bp.data_ptr(), b2.data_ptr(), st))
+        if B % (t + 1) == 0 and n * n * (B // (t + 1)) * 8 <= 1 << 30:
+            # the whole protocol as one device call (hbmpc_dev_prandbit_parties): with the threshold at 2^30 (ONE launch where the shape's
+            # tables fit a workgroup's LDS and the batch is small; `parties_call_form` says which ran) and at 0 (the eight launches)
+            G = B // (t + 1)
+            b_q = torch.zeros((n, B), dtype=torch.int64, device=dev)  # the constant sharing of the bit 0
+            rb = torch.zeros((n, B), dtype=torch.int64, device=dev)
+            Y = torch.full((n, n, G), -1, dtype=torch.int64, device=dev)
+            Z = torch.zeros((n, G), dtype=torch.int64, device=dev)
+            rst = torch.zeros((n, G), dtype=torch.uint8, device=dev)
+
+            def whole():
+                return fr.prandbit_parties(gl, contrib.data_ptr(), b_q.data_ptr(), n, t, B, lk, S, bad.data_ptr(), P, R2, Q, rb.data_ptr(), Y.data_ptr(),
+                                           Z.data_ptr(), opened.data_ptr(), bp.data_ptr(), b2.data_ptr(), rst.data_ptr(), stream=st)
+
+            for name, fused in (("one", 1 << 30), ("launches", 0)):
+                fr.set_fused_prandbit(fused)
+                Y.fill_(-1)
+                row[f"parties_call_{name}_ms"] = timed(whole)
+                torch.cuda.synchronize()
+                if fused:
+                    row["parties_call_form"] = "one launch" if bool((Y == -1).all()) else "separate launches"  # the one launch leaves the workspace alone
+            fr.set_fused_prandbit(pkg.hbmpc.FUSED_PRANDBIT_DEFAULT)
         if not args.no_baseline and (n, t) == (16, 5) and B <= 4096:
             # the same one-party conversion with the element-wise calls: 2 launches per set
             r256 = torch.zeros((Town, B, 4), dtype=torch.int64, device=dev)
