@@ -1027,7 +1027,13 @@ ShareErrorCode hbmpc_set_field_impl(hbmpc_ctx* ctx, int impl);
  * on = 3 keeps the matrix cores but gives every evaluation point its own table row, where the default takes the points of
  * a large encode in pairs (k, k + size/2) -- alpha_{k + size/2} = -alpha_k on a domain of roots of unity, so the even and
  * the odd coefficients' digit sums are computed once and added / subtracted: half the matrix-core work and LDS operand
- * traffic per output (csrc/kernels_mfma_bfly.hpp).
+ * traffic per output (csrc/kernels_mfma_bfly.hpp);
+ * on = 4 keeps the point pairs but not the loader wave of the plain chunk-major encode: by default one wave of every
+ * workgroup streams the inputs as whole lines into a ring of LDS slots and the others only compute and store
+ * (csrc/kernels_mfma_bfly_ring.hpp, taken when one role of 4 or 8 pairs and the ring fit the LDS); with 4 every wave
+ * gathers its own operands as before.  The default takes the loader form from four 32-chunk tiles per compute wave on
+ * (393 216 chunks on 256 CUs; below that its longer way to the first tile costs more than the whole-line reads save);
+ * on = 5 takes it at every batch size (test aid).  Same bytes in every mode.
  * A Goldilocks context has the same switch: for 2 <= d + 1 <= 16 its encodes on domains beyond 16 points run on the
  * matrix cores from 4 096 chunks, its decodes from 2 048 chunks when they are a single launch (exactly d + t + 1 senders)
  * and beyond the small-batch range (8 192 chunks) otherwise (csrc/kernels_mfma_gl.hpp: the table is a few KB, fits the

@@ -24,6 +24,7 @@
 #include "kernels_triplegen_wg.hpp"
 #include "kernels_randbit_wg.hpp"
 #include "kernels_prandbit_wg.hpp"
+#include "bfly_ring_plan.hpp"
 #include "launchers.hpp"
 #include "tables.hpp"
 #include "tables_mfma.hpp"
@@ -91,6 +92,8 @@ struct hbmpc_ctx {
     bool gather_row_copies = false;                // hbmpc_dev_gather_party_major: take the per-row peer copies even where the 2-D copy applies (A/B aid)
     bool list_rows_in_kernel = true;               // the producers' mixing step writes the parties' lists itself (k_mfma_bfly<.., LISTS>)
     bool mfma_bfly = true;                         // large encodes take the domain points in pairs (kernels_mfma_bfly.hpp)
+    int mfma_ring = 1;                             // the plain chunk-major point-pair encode reads through a loader wave and an LDS ring (kernels_mfma_bfly_ring.hpp):
+                                                   // 1 = from bfly_ring_min_tiles on, 0 = never, 2 = at every size (hbmpc_set_matrix_cores 4 / 5)
     bool mfma_team = true;                         // batches with fewer tiles than waves: a workgroup per tile (kernels_mfma_team.hpp)
     size_t mfma_min_gold = 4096;                   // Goldilocks encodes (tiny tables, one workgroup kind): from this many chunks
     size_t mfma_min_gold_direct = 2048;            // Goldilocks decodes without OEC rounds (one launch): flat ~7 us against a wave-per-chunk kernel that grows
@@ -430,6 +433,9 @@ extern "C" ShareErrorCode hbmpc_set_matrix_cores(hbmpc_ctx* ctx, int on, size_t 
     ctx->matrix_cores = on != 0;
     ctx->mfma_team = on != 2;  // 2: without the workgroup-per-tile kernel of small batches (A/B aid)
     ctx->mfma_bfly = on != 3;  // 3: large encodes with one table row per point instead of per point pair (A/B aid)
+    // 4: the point-pair encode without the loader wave and its LDS ring, every wave gathering its own inputs (A/B aid); 5: with them at
+    // every batch size, not only where they pay (test aid: a few tiles then reach every state of the ring)
+    ctx->mfma_ring = on == 4 ? 0 : on == 5 ? 2 : 1;
     if (min_chunks) {
         ctx->mfma_min_gold = std::min<size_t>(min_chunks, 4096);
         ctx->mfma_min_gold_direct = std::min<size_t>(min_chunks, 2048);
@@ -817,6 +823,9 @@ static bool run_mfma(hbmpc_ctx* ctx, const EncodeRoute& r, const uint32_t* x, si
     for (unsigned p = 0; p < y.parties; ++p) {
         a.in = (const uint8_t*)x + (size_t)p * G * dp1 * 32;
         a.out = lists && lists->others ? (uint8_t*)lists->others : (uint8_t*)y.y + (size_t)p * n * a.out_stride * 32;
+        // the shape and the batch size decide (bfly_ring_plan.hpp), the same for every party
+        const bool ring = ctx->mfma_ring == 2 || (ctx->mfma_ring == 1 && a.nroles == 1 && mf::bfly_ring_ntiles(G) >= mf::bfly_ring_min_tiles((size_t)a.role_nwg[0]));
+        if (ring && launch_mfma_bfly_ring(mi, a, ctx->device, s)) continue;
         if (!launch_mfma_bfly(mi, a, ctx->device, s)) return false;  // only the first party's launch can decline: the shape decides
     }
     return true;

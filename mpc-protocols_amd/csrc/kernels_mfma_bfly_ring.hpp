@@ -1,0 +1,175 @@
+// kernels_mfma_bfly_ring.hpp -- the ring form of the plain chunk-major paired-point encode (kernels_mfma_bfly.hpp: same table, same
+// pairs, same bytes out), the headline compute_shares kernel.
+//
+// Workgroup = CW compute waves + 1 LOADER wave.  The loader streams the workgroup's 32-chunk tiles as whole lines -- lane l takes the
+// 16-byte piece 64 i + l of a tile's M KB, so a load instruction touches 8 lines instead of the 32 of a lane-pair-per-chunk gather --
+// by LDS-DMA (global_load_lds_dwordx4: no data registers) into a ring of S LDS slots behind the table, D tiles in flight, and
+// publishes a slot when a counted vmcnt wait says its tile has landed.  The compute waves issue no vector-memory loads at all: poll
+// the slot's flag, M ds_read_b128 (chunk c, coefficient i, half h at 32 M c + 32 i + 16 h), free the slot, then flip, pairs and plain
+// conditional stores -- nothing in their loop waits on vmcnt, so the stores are fire-and-forget and the STATIC / dropped-store
+// machinery of k_mfma_bfly is not needed; one input register set instead of two.  The HBM latency and the LDS trip sit in the
+// loader's time.  The schedule (which tile, whose, which slot, which flag value) is bfly_ring_plan.hpp, simulated on the CPU by
+// tests/cpp/bfly_ring_sim.cpp; there is one barrier, after the table load and the zeroing of the flags, and none after it.
+// Measured forms and shapes: profiles/ring_encode_sweep.txt (tools/ubench_bfly_ring.hip).
+#pragma once
+#include "bfly_ring_plan.hpp"
+#include "kernels_mfma_bfly.hpp"
+
+namespace hbmpc {
+namespace mf {
+
+// one LDS-DMA piece: lane l's 16 bytes at sbase + voff land at lds_dst + 16 l (sbase, lds_dst wave-uniform).  M0 is compiler-reserved:
+// saved and restored inside the statement; the nop covers a base or destination fresh from a v_readfirstlane.
+HB_DEV void ring_dma16(const uint8_t* sbase, uint32_t voff, uint32_t lds_dst) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(sbase), "s"(lds_dst)
+                 : "memory");
+}
+// the flag words are read and written as LDS words (a volatile access through a generic pointer would be a flat one and wait for vmcnt)
+using ring_flag_t = __attribute__((address_space(3))) volatile uint32_t;
+HB_DEV uint32_t ring_flag(const ring_flag_t* p) { return __builtin_amdgcn_readfirstlane(*p); }
+
+template <int M, int CW, int NP, int S, int D>
+__global__ __launch_bounds__(64 * (CW + 1)) void k_mfma_bfly_ring(MfmaRowsArgs a) {
+    static_assert(bfly_ring_shape_ok(M, NP, BflyRingShape{CW, S, D}), "ring shape");
+    static_assert(M * (D - 1) <= 63, "vmcnt counts to 63");
+    constexpr int ROWB = M * 1024 + MF_BFLY_BIAS;
+    constexpr int NT = 64 * (CW + 1);
+    constexpr int TILEB = M * 1024;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];  // NP * ROWB, S slots, filled[S], freed[S]
+    const int blk8 = (int)blockIdx.x >> 3;
+    const uint32_t wg_in_role = (uint32_t)a.blk_idx[blk8] * 8 + (blockIdx.x & 7);
+    const MfmaRole role = a.role[0];  // one role
+    const uint32_t role_wgs = (uint32_t)a.role_nwg[0];
+    {
+        const uint8_t* src = a.table + (size_t)role.row0 * ROWB;
+        constexpr int pieces = NP * (ROWB / 16);
+        for (int p = threadIdx.x; p < pieces; p += NT)
+            *reinterpret_cast<v4i*>(lds + (size_t)p * 16) = *reinterpret_cast<const v4i*>(src + (size_t)p * 16);
+    }
+    uint8_t* const ring = lds + bfly_ring_table_bytes(M, NP);
+    ring_flag_t* const filled = (ring_flag_t*)(lds + bfly_ring_flags_offset(M, NP, S));
+    ring_flag_t* const freed = filled + S;
+    if (threadIdx.x < 2 * S) filled[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t nitems = (uint32_t)bfly_ring_items(bfly_ring_ntiles(a.G), role_wgs, wg_in_role, CW);
+    auto tile_of = [&](uint32_t q) { return bfly_ring_tile(role_wgs, wg_in_role, CW, q); };
+    if (wave == CW) {
+        // ---- the loader
+        if (nitems == 0) return;
+        const size_t total = a.G * (size_t)(M * 32);
+        auto wait_freed = [&](uint32_t q) {
+            if (q >= S) {
+                const uint32_t need = q / S;  // the sequence number of item q - S
+                while (ring_flag(freed + q % S) != need) __builtin_amdgcn_s_sleep(1);
+            }
+        };
+        auto publish = [&](uint32_t q) { filled[q % S] = q / S + 1; };
+        // this lane's piece offsets inside a tile; in the input's last tile, pieces past the end read its last 16 bytes
+        auto piece = [&](size_t tb, int i) {
+            const uint32_t off = (uint32_t)(i * 64 + lane) * 16u;
+            const size_t left = total - tb;  // >= 16: the tile exists
+            return left >= (size_t)TILEB || off + 16 <= left ? off : (uint32_t)(left - 16);
+        };
+        const uint32_t ring_lds = (uint32_t)(uintptr_t)ring;  // the LDS byte address: the low word of the flat address
+        for (uint32_t q = 0; q < nitems; ++q) {
+            wait_freed(q);
+            const size_t tb = tile_of(q) * (size_t)(32 * M * 32);
+            const uint32_t dst = __builtin_amdgcn_readfirstlane(ring_lds + (q % S) * TILEB);
+#pragma unroll
+            for (int i = 0; i < M; ++i) ring_dma16(a.in + tb, piece(tb, i), dst + i * 1024);
+            if (q + 1 >= D) {
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(M * (D - 1)) : "memory");
+                publish(q + 1 - D);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        for (uint32_t q = nitems >= D - 1 ? nitems - (D - 1) : 0; q < nitems; ++q) publish(q);
+        return;
+    }
+    // ---- a compute wave
+    const int c = lane & 31, h = lane >> 5;
+    const Half H = make_half(h);
+    for (uint32_t q = wave; q < nitems; q += CW) {
+        const uint32_t slot = q % S, seq = q / S + 1;
+        while (ring_flag(filled + slot) != seq) __builtin_amdgcn_s_sleep(1);
+        asm volatile("" ::: "memory");  // the data reads stay below the poll
+        v4i data[M];
+        {
+            const uint8_t* sp = ring + slot * TILEB + c * (M * 32) + 16 * h;
+#pragma unroll
+            for (int i = 0; i < M; ++i) data[i] = *reinterpret_cast<const v4i*>(sp + i * 32);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        freed[slot] = seq;
+#pragma unroll
+        for (int i = 0; i < M; ++i) data[i] = flip(data[i]);
+        const size_t t = tile_of(q);
+        const size_t gi = t * 32 + c;
+        const bool live = gi < a.G;
+        const uint32_t g = (uint32_t)(live ? gi : a.G - 1);
+        const uint32_t qo = g * (a.out_party_major ? 32u : (uint32_t)a.out_stride * 32u) + 16u * h;
+        auto store_row = [&](uint32_t k, bool exists, const uint32_t (&Rw)[4]) {
+            uint8_t* qb = a.out_party_major ? a.out + (size_t)k * a.out_stride * 32 : a.out + (size_t)k * 32;  // wave-uniform
+            if (exists && live) *reinterpret_cast<uint4*>(qb + qo) = make_uint4(Rw[0], Rw[1], Rw[2], Rw[3]);
+        };
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const uint8_t* cur = lds + (size_t)p * ROWB;
+            v16i accE, accT;
+            {
+                const v4i* bp = reinterpret_cast<const v4i*>(cur + M * 1024 + h * 64);
+                const v4i e0 = bp[0], e1 = bp[1], e2 = bp[2], e3 = bp[3];
+                const v4i t0 = bp[8], t1 = bp[9], t2 = bp[10], t3 = bp[11];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    accE[k] = e0[k], accE[4 + k] = e1[k], accE[8 + k] = e2[k], accE[12 + k] = e3[k];
+                    accT[k] = t0[k], accT[4 + k] = t1[k], accT[8 + k] = t2[k], accT[12 + k] = t3[k];
+                }
+            }
+            {   // the M MFMAs: even inputs into accE, odd into accT (two independent chains); A operands three slabs ahead
+                constexpr int AD = 3;
+                const uint8_t* tab_lane = cur + lane * 16;
+                v4i av[AD];
+#pragma unroll
+                for (int i = 0; i < AD - 1 && i < M; ++i) av[i] = *reinterpret_cast<const v4i*>(tab_lane + i * 1024);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < M; ++i) {
+                    if (i + AD - 1 < M) av[(i + AD - 1) % AD] = *reinterpret_cast<const v4i*>(tab_lane + (i + AD - 1) * 1024);
+                    if (i & 1) accT = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[i % AD], data[i], accT, 0, 0, 0);
+                    else accE = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[i % AD], data[i], accE, 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            uint32_t pe[8], pt[8];
+            gather_pairs(accE, pe);
+            gather_pairs(accT, pt);
+            uint32_t k32 = (uint32_t)(role.row0 + p);
+            asm volatile("" : "+s"(k32));  // the output row bases are recomputed, not kept per unrolled pair (scalar registers)
+            {
+                uint64_t T[4];
+                uint32_t Rw[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) T[j] = (uint64_t)(pe[2 * j + 1] + pt[2 * j + 1]) * H.k16 + (pe[2 * j] + pt[2 * j]);
+                reduce_words(T, Rw, H);
+                store_row(k32, true, Rw);
+            }
+            const bool partner = (int)k32 + a.half < a.nout;
+            if (partner) {
+                uint64_t T[4];
+                uint32_t Rw[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) T[j] = (uint64_t)(pe[2 * j + 1] - pt[2 * j + 1]) * H.k16 + (pe[2 * j] - pt[2 * j]);
+                reduce_words(T, Rw, H);
+                store_row(k32 + (uint32_t)a.half, true, Rw);
+            }
+        }
+    }
+}
+
+}  // namespace mf
+}  // namespace hbmpc

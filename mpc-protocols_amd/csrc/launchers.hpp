@@ -107,6 +107,9 @@ inline bool launch_mfma_bfly(int m, const mf::MfmaRowsArgs& a, int device, hipSt
     return launch_mfma_bfly_a(m, a, device, s) || launch_mfma_bfly_b(m, a, device, s) || launch_mfma_bfly_c(m, a, device, s) ||
            launch_mfma_bfly_d(m, a, device, s);
 }
+// the ring form of the plain chunk-major paired-point encode (kernels_mfma_bfly_ring.hpp: a loader wave fills an LDS ring with whole
+// lines); false, with nothing enqueued, for every shape bfly_ring_plan.hpp does not take -- the caller then uses launch_mfma_bfly
+bool launch_mfma_bfly_ring(int m, const mf::MfmaRowsArgs& a, int device, hipStream_t s);
 // small batches: one wave per chunk, one evaluation point / one table row per lane (k_eval_wide, k_batch_recover_wide)
 void launch_eval_wide(int impl, const uint32_t* x, size_t G, int n, int dp1, const uint32_t* alpha, EvalOut y, hipStream_t s);
 void launch_eval_wide_dot(const uint32_t* x, size_t G, int n, int dp1, const uint32_t* vmat, EvalOut y, hipStream_t s);  // U29, vmat [n][dp1] <= 48 KB
