@@ -27,6 +27,91 @@ namespace mf {
 
 constexpr int MF_BFLY_BIAS = 256;
 
+// ---- Pieces shared by the point-pair kernels: k_mfma_bfly below, k_mfma_bfly_ring (kernels_mfma_bfly_ring.hpp) and their
+// laboratory forms (tools/kernels_mfma_bfly_lab.hpp, tools/kernels_mfma_bfly_ring_lab.hpp).  Only pieces that leave the library
+// kernels' instructions exactly as they were when written in place are taken out (profiles/bfly_shared_body.txt): hipcc
+// simplifies a function on its own before it inlines it, and for most of the rest that reorders the kernel.
+
+// the table rows of a workgroup of NT threads into the LDS, 16 bytes a thread and step
+template <int NT>
+HB_DEV void bfly_table_to_lds(uint8_t* lds, const uint8_t* src, int pieces) {
+    for (int p = threadIdx.x; p < pieces; p += NT)
+        *reinterpret_cast<v4i*>(lds + (size_t)p * 16) = *reinterpret_cast<const v4i*>(src + (size_t)p * 16);
+}
+
+// one pair of one tile: the digit pairs of E_k (pe) and T_k (pt) from the table row at `cur` and the tile's B operands.
+// ABL: the timing-only ablations of the laboratory forms (the library instantiates ABL = 0): 2 = no MFMAs (EVERY dword of every
+// loaded input is folded into the accumulators), 4 = no LDS operand reads either
+template <int M, int ABL = 0>
+HB_DEV void bfly_pair(const uint8_t* cur, int lane, int h, const v4i (&data)[M], uint32_t (&pe)[8], uint32_t (&pt)[8]) {
+    v16i accE, accT;
+    {
+        const v4i* bp = reinterpret_cast<const v4i*>(cur + M * 1024 + h * 64);
+        const v4i e0 = bp[0], e1 = bp[1], e2 = bp[2], e3 = bp[3];
+        const v4i t0 = bp[8], t1 = bp[9], t2 = bp[10], t3 = bp[11];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            accE[k] = e0[k], accE[4 + k] = e1[k], accE[8 + k] = e2[k], accE[12 + k] = e3[k];
+            accT[k] = t0[k], accT[4 + k] = t1[k], accT[8 + k] = t2[k], accT[12 + k] = t3[k];
+        }
+    }
+    {   // the M MFMAs: even inputs into accE, odd into accT (two independent chains); A operands three slabs ahead
+        constexpr int D = 3;
+        const uint8_t* tab_lane = cur + lane * 16;
+        v4i av[D];
+#pragma unroll
+        for (int i = 0; i < D - 1 && i < M; ++i) av[i] = *reinterpret_cast<const v4i*>(tab_lane + i * 1024);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < M; ++i) {
+            if (i + D - 1 < M && !(ABL & 4)) av[(i + D - 1) % D] = *reinterpret_cast<const v4i*>(tab_lane + (i + D - 1) * 1024);
+            if (ABL & 2) {  // no MFMA: every loaded dword of input i (and of the slab, unless ABL & 4) is folded into the accumulators
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int mix = (ABL & 4) ? data[i][k] : (av[i % D][k] ^ data[i][k]);
+                    if (i & 1) accT[(4 * i + k) & 15] ^= mix;
+                    else accE[(4 * i + k) & 15] ^= mix;
+                }
+            } else if (i & 1) accT = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[i % D], data[i], accT, 0, 0, 0);
+            else accE = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[i % D], data[i], accE, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    gather_pairs(accE, pe);
+    gather_pairs(accT, pt);
+}
+
+// where the outputs of chunk c of tile t go: chunks past the end are computed as the last chunk and not stored
+struct BflyOut {
+    bool live;
+    uint32_t g;   // the chunk, clamped
+    uint32_t qo;  // this lane's byte offset behind the base of an output row
+};
+HB_DEV BflyOut bfly_out(const MfmaRowsArgs& a, size_t t, int c, int h) {
+    const size_t gi = t * 32 + c;
+    BflyOut o;
+    o.live = gi < a.G;
+    o.g = (uint32_t)(o.live ? gi : a.G - 1);
+    o.qo = o.g * (a.out_party_major ? 32u : (uint32_t)a.out_stride * 32u) + 16u * h;
+    return o;
+}
+
+// as many dropped stores as a tile issues: the loop header then sees the same queue behind the first loads on entry as on the back
+// edge (hipcc merges the two states to the stricter wait)
+template <int N>
+HB_DEV void bfly_dropped_stores(uint8_t* out) {
+    const v4i z = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < N; ++k) __builtin_amdgcn_raw_buffer_store_b128(z, rt_rsrc(out, 0u), (int)RT_OOB, 0, 0);
+}
+
+// DEG: output k of the lane pair's chunk exists and is nonzero -> the degree is at least k
+HB_DEV void bfly_note_degree(uint32_t& degree, uint32_t k, bool exists, const uint32_t (&Rw)[4]) {
+    const uint32_t any = Rw[0] | Rw[1] | Rw[2] | Rw[3];
+    const auto both = __builtin_amdgcn_permlane32_swap(any, any, false, false);  // [0]: the low half's value, [1]: the high half's
+    if (exists && (both[0] | both[1]) != 0 && k > degree) degree = k;
+}
+
 // NP > 0: every role has exactly NP pairs (the host plans it so) and the pair loop is unrolled
 // (Timing-only ablations and the whole-line read path of round 3 live in tools/kernels_mfma_bfly_lab.hpp.)
 // TRIPLE: the encode of triple generation -- the inputs are the local products a b - r2t of three arrays
@@ -55,7 +140,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_mfma_bfly(MfmaRowsArgs a) {
 #pragma unroll
     for (int k = 1; k < MF_MAX_ROLES; ++k)
         if (k == role_id) role = a.role[k], role_wgs = a.role_nwg[k];
-    {
+    {   // bfly_table_to_lds in place: through the function, the NP = 0 instances come out with other instructions
         const uint8_t* src = a.table + (size_t)role.row0 * ROWB;
         const int pieces = role.nrows * (ROWB / 16);
         for (int p = threadIdx.x; p < pieces; p += NT)
@@ -134,43 +219,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_mfma_bfly(MfmaRowsArgs a) {
             }
         }
         [[maybe_unused]] uint32_t degree = 0;
-        [[maybe_unused]] auto note_degree = [&](uint32_t k, bool exists, const uint32_t (&Rw)[4]) {
-            const uint32_t any = Rw[0] | Rw[1] | Rw[2] | Rw[3];
-            const auto both = __builtin_amdgcn_permlane32_swap(any, any, false, false);  // [0]: the low half's value, [1]: the high half's
-            if (exists && (both[0] | both[1]) != 0 && k > degree) degree = k;
-        };
 #pragma unroll
         for (int p = 0; p < (STATIC ? NP : role.nrows); ++p) {
-            const uint8_t* cur = lds + (size_t)p * ROWB;
-            v16i accE, accT;
-            {
-                const v4i* bp = reinterpret_cast<const v4i*>(cur + M * 1024 + h * 64);
-                const v4i e0 = bp[0], e1 = bp[1], e2 = bp[2], e3 = bp[3];
-                const v4i t0 = bp[8], t1 = bp[9], t2 = bp[10], t3 = bp[11];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    accE[k] = e0[k], accE[4 + k] = e1[k], accE[8 + k] = e2[k], accE[12 + k] = e3[k];
-                    accT[k] = t0[k], accT[4 + k] = t1[k], accT[8 + k] = t2[k], accT[12 + k] = t3[k];
-                }
-            }
-            {   // the M MFMAs: even inputs into accE, odd into accT (two independent chains); A operands three slabs ahead
-                constexpr int D = 3;
-                const uint8_t* tab_lane = cur + lane * 16;
-                v4i av[D];
-#pragma unroll
-                for (int i = 0; i < D - 1 && i < M; ++i) av[i] = *reinterpret_cast<const v4i*>(tab_lane + i * 1024);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < M; ++i) {
-                    if (i + D - 1 < M) av[(i + D - 1) % D] = *reinterpret_cast<const v4i*>(tab_lane + (i + D - 1) * 1024);
-                    if (i & 1) accT = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[i % D], data[i], accT, 0, 0, 0);
-                    else accE = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[i % D], data[i], accE, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
             uint32_t pe[8], pt[8];
-            gather_pairs(accE, pe);
-            gather_pairs(accT, pt);
+            bfly_pair<M>(lds + (size_t)p * ROWB, lane, h, data, pe, pt);
             uint32_t k32 = (uint32_t)(role.row0 + p);
             asm volatile("" : "+s"(k32));  // the output row bases are recomputed, not kept per unrolled pair (scalar registers)
             {
@@ -180,7 +232,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_mfma_bfly(MfmaRowsArgs a) {
                 for (int j = 0; j < 4; ++j) T[j] = (uint64_t)(pe[2 * j + 1] + pt[2 * j + 1]) * H.k16 + (pe[2 * j] + pt[2 * j]);
                 reduce_words(T, Rw, H);
                 store_row(out, k32, true, live, qo, Rw, sc);
-                if constexpr (DEG) note_degree(k32, true, Rw);
+                if constexpr (DEG) bfly_note_degree(degree, k32, true, Rw);
             }
             const bool partner = (int)k32 + a.half < a.nout;
             if (STATIC || partner) {
@@ -190,7 +242,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_mfma_bfly(MfmaRowsArgs a) {
                 for (int j = 0; j < 4; ++j) T[j] = (uint64_t)(pe[2 * j + 1] - pt[2 * j + 1]) * H.k16 + (pe[2 * j] - pt[2 * j]);
                 reduce_words(T, Rw, H);
                 store_row(out, k32 + (uint32_t)a.half, partner, live, qo, Rw, sc);
-                if constexpr (DEG) note_degree(k32 + (uint32_t)a.half, partner, Rw);
+                if constexpr (DEG) bfly_note_degree(degree, k32 + (uint32_t)a.half, partner, Rw);
             }
         }
         if constexpr (DEG) {  // one more counted store: lanes that do not write get an offset beyond the buffer
@@ -204,13 +256,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_mfma_bfly(MfmaRowsArgs a) {
         for (int i = 0; i < M; ++i) data[i] = flip(data[i]);
         pairs_of_tile(t, data, a.out);
     };
-    auto dropped_stores = [&] {
-        // as many dropped stores as a tile issues: the loop header then sees the same queue behind the first loads on entry
-        // as on the back edge (hipcc merges the two states to the stricter wait)
-        const v4i z = {0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < 2 * NP + (DEG ? 1 : 0); ++k) __builtin_amdgcn_raw_buffer_store_b128(z, rt_rsrc(a.out, 0u), (int)RT_OOB, 0, 0);
-    };
+    auto dropped_stores = [&] { bfly_dropped_stores<2 * NP + (DEG ? 1 : 0)>(a.out); };
     if constexpr (TRIPLE) {
         using F = U29;
         constexpr int NS = (M + 1) / 2;  // slots: slot j holds coefficient 2 j + h of this lane's chunk

@@ -43,12 +43,7 @@ __global__ __launch_bounds__(64 * (CW + 1)) void k_mfma_bfly_ring(MfmaRowsArgs a
     const uint32_t wg_in_role = (uint32_t)a.blk_idx[blk8] * 8 + (blockIdx.x & 7);
     const MfmaRole role = a.role[0];  // one role
     const uint32_t role_wgs = (uint32_t)a.role_nwg[0];
-    {
-        const uint8_t* src = a.table + (size_t)role.row0 * ROWB;
-        constexpr int pieces = NP * (ROWB / 16);
-        for (int p = threadIdx.x; p < pieces; p += NT)
-            *reinterpret_cast<v4i*>(lds + (size_t)p * 16) = *reinterpret_cast<const v4i*>(src + (size_t)p * 16);
-    }
+    bfly_table_to_lds<NT>(lds, a.table + (size_t)role.row0 * ROWB, NP * (ROWB / 16));
     uint8_t* const ring = lds + bfly_ring_table_bytes(M, NP);
     ring_flag_t* const filled = (ring_flag_t*)(lds + bfly_ring_flags_offset(M, NP, S));
     ring_flag_t* const freed = filled + S;
@@ -107,47 +102,15 @@ __global__ __launch_bounds__(64 * (CW + 1)) void k_mfma_bfly_ring(MfmaRowsArgs a
         freed[slot] = seq;
 #pragma unroll
         for (int i = 0; i < M; ++i) data[i] = flip(data[i]);
-        const size_t t = tile_of(q);
-        const size_t gi = t * 32 + c;
-        const bool live = gi < a.G;
-        const uint32_t g = (uint32_t)(live ? gi : a.G - 1);
-        const uint32_t qo = g * (a.out_party_major ? 32u : (uint32_t)a.out_stride * 32u) + 16u * h;
+        const BflyOut o = bfly_out(a, tile_of(q), c, h);
         auto store_row = [&](uint32_t k, bool exists, const uint32_t (&Rw)[4]) {
             uint8_t* qb = a.out_party_major ? a.out + (size_t)k * a.out_stride * 32 : a.out + (size_t)k * 32;  // wave-uniform
-            if (exists && live) *reinterpret_cast<uint4*>(qb + qo) = make_uint4(Rw[0], Rw[1], Rw[2], Rw[3]);
+            if (exists && o.live) *reinterpret_cast<uint4*>(qb + o.qo) = make_uint4(Rw[0], Rw[1], Rw[2], Rw[3]);
         };
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-            const uint8_t* cur = lds + (size_t)p * ROWB;
-            v16i accE, accT;
-            {
-                const v4i* bp = reinterpret_cast<const v4i*>(cur + M * 1024 + h * 64);
-                const v4i e0 = bp[0], e1 = bp[1], e2 = bp[2], e3 = bp[3];
-                const v4i t0 = bp[8], t1 = bp[9], t2 = bp[10], t3 = bp[11];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    accE[k] = e0[k], accE[4 + k] = e1[k], accE[8 + k] = e2[k], accE[12 + k] = e3[k];
-                    accT[k] = t0[k], accT[4 + k] = t1[k], accT[8 + k] = t2[k], accT[12 + k] = t3[k];
-                }
-            }
-            {   // the M MFMAs: even inputs into accE, odd into accT (two independent chains); A operands three slabs ahead
-                constexpr int AD = 3;
-                const uint8_t* tab_lane = cur + lane * 16;
-                v4i av[AD];
-#pragma unroll
-                for (int i = 0; i < AD - 1 && i < M; ++i) av[i] = *reinterpret_cast<const v4i*>(tab_lane + i * 1024);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < M; ++i) {
-                    if (i + AD - 1 < M) av[(i + AD - 1) % AD] = *reinterpret_cast<const v4i*>(tab_lane + (i + AD - 1) * 1024);
-                    if (i & 1) accT = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[i % AD], data[i], accT, 0, 0, 0);
-                    else accE = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[i % AD], data[i], accE, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
             uint32_t pe[8], pt[8];
-            gather_pairs(accE, pe);
-            gather_pairs(accT, pt);
+            bfly_pair<M>(lds + (size_t)p * ROWB, lane, h, data, pe, pt);
             uint32_t k32 = (uint32_t)(role.row0 + p);
             asm volatile("" : "+s"(k32));  // the output row bases are recomputed, not kept per unrolled pair (scalar registers)
             {

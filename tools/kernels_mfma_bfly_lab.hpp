@@ -1,9 +1,12 @@
 // kernels_mfma_bfly_lab.hpp -- laboratory forms of k_mfma_bfly (csrc/kernels_mfma_bfly.hpp), for the microbenchmarks under tools/ only;
-// nothing here is compiled into the library.  k_mfma_bfly_lab<M, WAVES, NP, ABL, TRIPLE, TRIPLE_DEPTH, DEG, LINES>: the production
-// kernel's text plus
+// nothing here is compiled into the library.  k_mfma_bfly_lab<M, WAVES, NP, ABL, TRIPLE, TRIPLE_DEPTH, DEG, LINES> calls the
+// production kernel's own pieces where that header has them as functions (the table copy, bfly_pair with its ABL hooks, the output
+// offsets, the degree, the dropped stores); the input loads, the store, the tile loop and the TRIPLE walk are written in place in
+// k_mfma_bfly -- as functions they change its instructions (profiles/bfly_shared_body.txt) -- and are COPIES of that text here,
+// without LISTS and DEG's store_rows, kept equal by hand.  On top of it:
 //   ABL    timing-only ablations: 1 = no epilogue arithmetic (the stores stay and depend on every accumulator register),
-//          2 = no MFMAs (EVERY dword of every loaded input is folded into the accumulators), 4 = no LDS operand reads either,
-//          8 = (TRIPLE) no field products (the three operands of every element are XOR-ed: every load stays)
+//          2 = no MFMAs (EVERY dword of every loaded input is folded into the accumulators), 4 = no LDS operand reads either
+//          (both in bfly_pair), 8 = (TRIPLE) no field products (the three operands of every element are XOR-ed: every load stays)
 //   LINES  (chunk-major inputs) a tile's M KB requested as whole lines -- lane l takes 16-byte piece i * 64 + l -- and turned into
 //          the operand layout through a wave-private LDS slot (chunk c at c * (32 M + 16) bytes), instead of M 16-byte gathers per
 //          lane at a stride of 32 M bytes; bit-identical, not faster (profiles/r03_mfma_bfly_followup.txt)
@@ -15,6 +18,25 @@
 
 namespace hbmpc {
 namespace mf {
+
+// this half's four words of output k (pe + pt) or of its partner (pe - pt, MINUS) for both laboratory kernels: the sum or
+// difference of the un-normalised digit pairs, one carry pass and reduction; ABL & 1: four adds instead.  (The library kernels
+// keep these lines in place: as a function they reorder the instructions of every instance.)
+template <bool MINUS, int ABL>
+HB_DEV void bfly_words_lab(const uint32_t (&pe)[8], const uint32_t (&pt)[8], const Half& H, uint32_t (&Rw)[4]) {
+    uint32_t s[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s[j] = MINUS ? pe[j] - pt[j] : pe[j] + pt[j];
+    if constexpr ((ABL & 1) != 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Rw[j] = s[2 * j] + s[2 * j + 1];
+    } else {
+        uint64_t T[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) T[j] = (uint64_t)s[2 * j + 1] * H.k16 + s[2 * j];
+        reduce_words(T, Rw, H);
+    }
+}
 
 template <int M>
 constexpr int bfly_slot_bytes() { return 32 * (M * 32 + 16); }
@@ -31,12 +53,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_mfma_bfly_lab(MfmaRowsArgs a) {
 #pragma unroll
     for (int k = 1; k < MF_MAX_ROLES; ++k)
         if (k == role_id) role = a.role[k], role_wgs = a.role_nwg[k];
-    {
-        const uint8_t* src = a.table + (size_t)role.row0 * ROWB;
-        const int pieces = role.nrows * (ROWB / 16);
-        for (int p = threadIdx.x; p < pieces; p += NT)
-            *reinterpret_cast<v4i*>(lds + (size_t)p * 16) = *reinterpret_cast<const v4i*>(src + (size_t)p * 16);
-    }
+    bfly_table_to_lds<NT>(lds, a.table + (size_t)role.row0 * ROWB, role.nrows * (ROWB / 16));
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
     const Half H = make_half(h);
@@ -99,83 +116,29 @@ __global__ __launch_bounds__(64 * WAVES) void k_mfma_bfly_lab(MfmaRowsArgs a) {
     };
     // the pairs of one tile from its B operands (sign-flipped bytes)
     auto pairs_of_tile = [&](size_t t, const v4i (&data)[M], uint8_t* out) {
-        const size_t gi = t * 32 + c;
-        const bool live = gi < a.G;
-        const uint32_t g = (uint32_t)(live ? gi : a.G - 1);
-        const uint32_t qo = g * (a.out_party_major ? 32u : (uint32_t)a.out_stride * 32u) + 16u * h;
+        const BflyOut o = bfly_out(a, t, c, h);
         [[maybe_unused]] uint32_t degree = 0;
-        [[maybe_unused]] auto note_degree = [&](uint32_t k, bool exists, const uint32_t (&Rw)[4]) {
-            const uint32_t any = Rw[0] | Rw[1] | Rw[2] | Rw[3];
-            const auto both = __builtin_amdgcn_permlane32_swap(any, any, false, false);  // [0]: the low half's value, [1]: the high half's
-            if (exists && (both[0] | both[1]) != 0 && k > degree) degree = k;
-        };
 #pragma unroll
         for (int p = 0; p < (STATIC ? NP : role.nrows); ++p) {
-            const uint8_t* cur = lds + (size_t)p * ROWB;
-            v16i accE, accT;
-            {
-                const v4i* bp = reinterpret_cast<const v4i*>(cur + M * 1024 + h * 64);
-                const v4i e0 = bp[0], e1 = bp[1], e2 = bp[2], e3 = bp[3];
-                const v4i t0 = bp[8], t1 = bp[9], t2 = bp[10], t3 = bp[11];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    accE[k] = e0[k], accE[4 + k] = e1[k], accE[8 + k] = e2[k], accE[12 + k] = e3[k];
-                    accT[k] = t0[k], accT[4 + k] = t1[k], accT[8 + k] = t2[k], accT[12 + k] = t3[k];
-                }
-            }
-            {   // the M MFMAs: even inputs into accE, odd into accT (two independent chains); A operands three slabs ahead
-                constexpr int D = 3;
-                const uint8_t* tab_lane = cur + lane * 16;
-                v4i av[D];
-#pragma unroll
-                for (int i = 0; i < D - 1 && i < M; ++i) av[i] = *reinterpret_cast<const v4i*>(tab_lane + i * 1024);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < M; ++i) {
-                    if (i + D - 1 < M && !(ABL & 4)) av[(i + D - 1) % D] = *reinterpret_cast<const v4i*>(tab_lane + (i + D - 1) * 1024);
-                    if (ABL & 2) {  // no MFMA: every loaded dword of input i (and of the slab, unless ABL & 4) is folded into the accumulators
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const int mix = (ABL & 4) ? data[i][k] : (av[i % D][k] ^ data[i][k]);
-                            if (i & 1) accT[(4 * i + k) & 15] ^= mix;
-                            else accE[(4 * i + k) & 15] ^= mix;
-                        }
-                    } else if (i & 1) accT = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[i % D], data[i], accT, 0, 0, 0);
-                    else accE = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[i % D], data[i], accE, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
             uint32_t pe[8], pt[8];
-            gather_pairs(accE, pe);
-            gather_pairs(accT, pt);
+            bfly_pair<M, ABL>(lds + (size_t)p * ROWB, lane, h, data, pe, pt);
             uint32_t k32 = (uint32_t)(role.row0 + p);
             asm volatile("" : "+s"(k32));  // the output row bases are recomputed, not kept per unrolled pair (scalar registers)
-            {
-                uint64_t T[4];
-                uint32_t Rw[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) T[j] = (uint64_t)(pe[2 * j + 1] + pt[2 * j + 1]) * H.k16 + (pe[2 * j] + pt[2 * j]);
-                if (ABL & 1) Rw[0] = pe[0] + pt[1] + pe[1] + pt[0], Rw[1] = pe[2] + pt[3] + pe[3] + pt[2], Rw[2] = pe[4] + pt[5] + pe[5] + pt[4], Rw[3] = pe[6] + pt[7] + pe[7] + pt[6];
-                else reduce_words(T, Rw, H);
-                store_row(out, k32, true, live, qo, Rw);
-                if constexpr (DEG) note_degree(k32, true, Rw);
-            }
+            uint32_t Rw[4];
+            bfly_words_lab<false, ABL>(pe, pt, H, Rw);
+            store_row(out, k32, true, o.live, o.qo, Rw);
+            if constexpr (DEG) bfly_note_degree(degree, k32, true, Rw);
             const bool partner = (int)k32 + a.half < a.nout;
             if (STATIC || partner) {
-                uint64_t T[4];
-                uint32_t Rw[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) T[j] = (uint64_t)(pe[2 * j + 1] - pt[2 * j + 1]) * H.k16 + (pe[2 * j] - pt[2 * j]);
-                if (ABL & 1) Rw[0] = pe[0] - pt[1] + pe[1] - pt[0], Rw[1] = pe[2] - pt[3] + pe[3] - pt[2], Rw[2] = pe[4] - pt[5] + pe[5] - pt[4], Rw[3] = pe[6] - pt[7] + pe[7] - pt[6];
-                else reduce_words(T, Rw, H);
-                store_row(out, k32 + (uint32_t)a.half, partner, live, qo, Rw);
-                if constexpr (DEG) note_degree(k32 + (uint32_t)a.half, partner, Rw);
+                bfly_words_lab<true, ABL>(pe, pt, H, Rw);
+                store_row(out, k32 + (uint32_t)a.half, partner, o.live, o.qo, Rw);
+                if constexpr (DEG) bfly_note_degree(degree, k32 + (uint32_t)a.half, partner, Rw);
             }
         }
         if constexpr (DEG) {  // one more counted store: lanes that do not write get an offset beyond the buffer
             const size_t db = a.G * 4;
             __builtin_amdgcn_raw_buffer_store_b32(degree, rt_rsrc(a.ncoeffs, (uint32_t)(db < 0xffffffe0ull ? db : 0xffffffe0ull)),
-                                                  (int)(live && h == 0 ? g * 4u : RT_OOB), 0, 0);
+                                                  (int)(o.live && h == 0 ? o.g * 4u : RT_OOB), 0, 0);
         }
     };
     auto process_tile = [&](size_t t, v4i (&data)[M]) {
@@ -189,13 +152,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_mfma_bfly_lab(MfmaRowsArgs a) {
         for (int i = 0; i < M; ++i) data[i] = flip(data[i]);
         pairs_of_tile(t, data, a.out);
     };
-    auto dropped_stores = [&] {
-        // as many dropped stores as a tile issues: the loop header then sees the same queue behind the first loads on entry
-        // as on the back edge (hipcc merges the two states to the stricter wait)
-        const v4i z = {0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < 2 * NP + (DEG ? 1 : 0); ++k) __builtin_amdgcn_raw_buffer_store_b128(z, rt_rsrc(a.out, 0u), (int)RT_OOB, 0, 0);
-    };
+    auto dropped_stores = [&] { bfly_dropped_stores<2 * NP + (DEG ? 1 : 0)>(a.out); };
     if constexpr (TRIPLE) {
         using F = U29;
         constexpr int NS = (M + 1) / 2;  // slots: slot j holds coefficient 2 j + h of this lane's chunk

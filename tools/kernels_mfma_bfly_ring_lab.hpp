@@ -1,5 +1,8 @@
-// kernels_mfma_bfly_ring_lab.hpp -- laboratory forms of k_mfma_bfly_ring (csrc/kernels_mfma_bfly_ring.hpp: the text of that kernel plus the
-// second loader form and timing-only ablations), for tools/ubench_bfly_ring.hip only; nothing here is compiled into the library.
+// kernels_mfma_bfly_ring_lab.hpp -- laboratory forms of k_mfma_bfly_ring (csrc/kernels_mfma_bfly_ring.hpp), for tools/ubench_bfly_ring.hip
+// only; nothing here is compiled into the library.  The table copy, the pair core (bfly_pair, with its ABL hooks) and the output
+// offsets are the library's own functions (csrc/kernels_mfma_bfly.hpp); the ring set-up, the LDS-DMA loader and a compute wave's take
+// of a slot are written in place in k_mfma_bfly_ring -- as functions they change its instructions (profiles/bfly_shared_body.txt) --
+// and are COPIES of that text here, kept equal by hand, next to the second loader form.
 //
 // Workgroup = CW compute waves + 1 loader wave.  The loader streams the workgroup's tiles as whole lines (lane l takes the 16-byte
 // piece 64 i + l of a tile's M KB) into a ring of S LDS slots behind the table, D tiles in flight; the compute waves issue no
@@ -11,6 +14,7 @@
 //   ABL   timing-only ablations as in kernels_mfma_bfly_lab.hpp: 1 no epilogue arithmetic, 2 no MFMAs, 4 no table reads
 #pragma once
 #include "../mpc-protocols_amd/csrc/kernels_mfma_bfly_ring.hpp"
+#include "kernels_mfma_bfly_lab.hpp"
 
 namespace hbmpc {
 namespace mf {
@@ -27,12 +31,7 @@ __global__ __launch_bounds__(64 * (CW + 1)) void k_mfma_bfly_ring_lab(MfmaRowsAr
     const uint32_t wg_in_role = (uint32_t)a.blk_idx[blk8] * 8 + (blockIdx.x & 7);
     const MfmaRole role = a.role[0];  // one role
     const uint32_t role_wgs = (uint32_t)a.role_nwg[0];
-    {
-        const uint8_t* src = a.table + (size_t)role.row0 * ROWB;
-        constexpr int pieces = NP * (ROWB / 16);
-        for (int p = threadIdx.x; p < pieces; p += NT)
-            *reinterpret_cast<v4i*>(lds + (size_t)p * 16) = *reinterpret_cast<const v4i*>(src + (size_t)p * 16);
-    }
+    bfly_table_to_lds<NT>(lds, a.table + (size_t)role.row0 * ROWB, NP * (ROWB / 16));
     uint8_t* const ring = lds + bfly_ring_table_bytes(M, NP);
     ring_flag_t* const filled = (ring_flag_t*)(lds + bfly_ring_flags_offset(M, NP, S));
     ring_flag_t* const freed = filled + S;
@@ -105,11 +104,6 @@ __global__ __launch_bounds__(64 * (CW + 1)) void k_mfma_bfly_ring_lab(MfmaRowsAr
     // ---- a compute wave
     const int c = lane & 31, h = lane >> 5;
     const Half H = make_half(h);
-    const uint32_t row_bytes = (uint32_t)([&] {
-        const size_t b = a.out_party_major ? a.G * 32 : a.G * a.out_stride * 32;
-        return b < 0xffffffe0ull ? b : 0xffffffe0ull;
-    }());
-    (void)row_bytes;
     for (uint32_t q = wave; q < nitems; q += CW) {
         const uint32_t slot = q % S, seq = q / S + 1;
         while (ring_flag(filled + slot) != seq) __builtin_amdgcn_s_sleep(1);
@@ -124,73 +118,22 @@ __global__ __launch_bounds__(64 * (CW + 1)) void k_mfma_bfly_ring_lab(MfmaRowsAr
         freed[slot] = seq;
 #pragma unroll
         for (int i = 0; i < M; ++i) data[i] = flip(data[i]);
-        const size_t t = tile_of(q);
-        const size_t gi = t * 32 + c;
-        const bool live = gi < a.G;
-        const uint32_t g = (uint32_t)(live ? gi : a.G - 1);
-        const uint32_t qo = g * (a.out_party_major ? 32u : (uint32_t)a.out_stride * 32u) + 16u * h;
+        const BflyOut o = bfly_out(a, tile_of(q), c, h);
         auto store_row = [&](uint32_t k, bool exists, const uint32_t (&Rw)[4]) {
             uint8_t* qb = a.out_party_major ? a.out + (size_t)k * a.out_stride * 32 : a.out + (size_t)k * 32;  // wave-uniform
-            if (exists && live) *reinterpret_cast<uint4*>(qb + qo) = make_uint4(Rw[0], Rw[1], Rw[2], Rw[3]);
+            if (exists && o.live) *reinterpret_cast<uint4*>(qb + o.qo) = make_uint4(Rw[0], Rw[1], Rw[2], Rw[3]);
         };
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-            const uint8_t* cur = lds + (size_t)p * ROWB;
-            v16i accE, accT;
-            {
-                const v4i* bp = reinterpret_cast<const v4i*>(cur + M * 1024 + h * 64);
-                const v4i e0 = bp[0], e1 = bp[1], e2 = bp[2], e3 = bp[3];
-                const v4i t0 = bp[8], t1 = bp[9], t2 = bp[10], t3 = bp[11];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    accE[k] = e0[k], accE[4 + k] = e1[k], accE[8 + k] = e2[k], accE[12 + k] = e3[k];
-                    accT[k] = t0[k], accT[4 + k] = t1[k], accT[8 + k] = t2[k], accT[12 + k] = t3[k];
-                }
-            }
-            {   // the M MFMAs: even inputs into accE, odd into accT (two independent chains); A operands three slabs ahead
-                constexpr int AD = 3;
-                const uint8_t* tab_lane = cur + lane * 16;
-                v4i av[AD];
-#pragma unroll
-                for (int i = 0; i < AD - 1 && i < M; ++i) av[i] = *reinterpret_cast<const v4i*>(tab_lane + i * 1024);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < M; ++i) {
-                    if (i + AD - 1 < M && !(ABL & 4)) av[(i + AD - 1) % AD] = *reinterpret_cast<const v4i*>(tab_lane + (i + AD - 1) * 1024);
-                    if (ABL & 2) {  // no MFMA: every loaded dword of input i (and of the slab, unless ABL & 4) is folded into the accumulators
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const int mix = (ABL & 4) ? data[i][k] : (av[i % AD][k] ^ data[i][k]);
-                            if (i & 1) accT[(4 * i + k) & 15] ^= mix;
-                            else accE[(4 * i + k) & 15] ^= mix;
-                        }
-                    } else if (i & 1) accT = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[i % AD], data[i], accT, 0, 0, 0);
-                    else accE = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[i % AD], data[i], accE, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
             uint32_t pe[8], pt[8];
-            gather_pairs(accE, pe);
-            gather_pairs(accT, pt);
+            bfly_pair<M, ABL>(lds + (size_t)p * ROWB, lane, h, data, pe, pt);
             uint32_t k32 = (uint32_t)(role.row0 + p);
             asm volatile("" : "+s"(k32));  // the output row bases are recomputed, not kept per unrolled pair (scalar registers)
-            {
-                uint64_t T[4];
-                uint32_t Rw[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) T[j] = (uint64_t)(pe[2 * j + 1] + pt[2 * j + 1]) * H.k16 + (pe[2 * j] + pt[2 * j]);
-                if (ABL & 1) Rw[0] = pe[0] + pt[1] + pe[1] + pt[0], Rw[1] = pe[2] + pt[3] + pe[3] + pt[2], Rw[2] = pe[4] + pt[5] + pe[5] + pt[4], Rw[3] = pe[6] + pt[7] + pe[7] + pt[6];
-                else reduce_words(T, Rw, H);
-                store_row(k32, true, Rw);
-            }
-            const bool partner = (int)k32 + a.half < a.nout;
-            if (partner) {
-                uint64_t T[4];
-                uint32_t Rw[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) T[j] = (uint64_t)(pe[2 * j + 1] - pt[2 * j + 1]) * H.k16 + (pe[2 * j] - pt[2 * j]);
-                if (ABL & 1) Rw[0] = pe[0] - pt[1] + pe[1] - pt[0], Rw[1] = pe[2] - pt[3] + pe[3] - pt[2], Rw[2] = pe[4] - pt[5] + pe[5] - pt[4], Rw[3] = pe[6] - pt[7] + pe[7] - pt[6];
-                else reduce_words(T, Rw, H);
+            uint32_t Rw[4];
+            bfly_words_lab<false, ABL>(pe, pt, H, Rw);
+            store_row(k32, true, Rw);
+            if ((int)k32 + a.half < a.nout) {  // the partner exists
+                bfly_words_lab<true, ABL>(pe, pt, H, Rw);
                 store_row(k32 + (uint32_t)a.half, true, Rw);
             }
         }
