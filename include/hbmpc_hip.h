@@ -208,7 +208,7 @@ void hbmpc_graph_destroy(hbmpc_graph* graph);
  * decode and returns the failing chunk's error where the reference's `?` would).  deal() / finish() are the two halves of a
  * producer's run (tests corrupt the dealt shares in between).  capture() = two eager runs + a recorded one; replay() launches
  * the recording (stream must be a real stream).  summary(): the last decode's hbmpc_recover_summary; verdict(): a producer's
- * {verifier checks that failed, first failing batch element} (preprocessing: both producers) -- both synchronise.
+ * {verifier checks that failed, lowest failing batch element} (preprocessing: both producers) -- both synchronise.
  * Errors: InvalidInput for shapes the reference rejects or unknown names, TypeMismatch for fpmul on a Goldilocks context. */
 typedef struct hbmpc_pipe hbmpc_pipe;
 ShareErrorCode hbmpc_pipe_triplegen_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream, hbmpc_pipe** pipe_out);
@@ -420,14 +420,15 @@ ShareErrorCode hbmpc_dev_batch_interpolate(hbmpc_ctx* ctx, const size_t* ids, si
  * and whether their constant terms agree): c0_out[G] = coefficient 0, degree_out[G] = DensePolynomial::degree().  Through all
  * n shares of an 8- or 16-point domain the kernel writes just these (36 bytes per column instead of 32 S); other shapes
  * interpolate into tmp_coeffs_dev[G][S] (required) and extract them.  hbmpc_dev_check_double_share_c0 is the test on two such
- * pairs: bad[0] += columns with degree_t != t, degree_2t != 2 t or c0_t != c0_2t, bad[1] = min(first such column). */
+ * pairs: bad[0] += columns with degree_t != t, degree_2t != 2 t or c0_t != c0_2t, bad[1] = min(bad[1], lowest such column). */
 ShareErrorCode hbmpc_dev_batch_interpolate_c0(hbmpc_ctx* ctx, const size_t* ids, size_t S, const U256* evals_dev, size_t row_stride,
                                               size_t G, size_t n, U256* tmp_coeffs_dev, U256* c0_out_dev, uint32_t* degree_out_dev,
                                               void* stream);
 ShareErrorCode hbmpc_dev_check_double_share_c0(hbmpc_ctx* ctx, const void* c0_t_dev, const uint32_t* degree_t_dev, const void* c0_2t_dev,
                                                const uint32_t* degree_2t_dev, size_t G, size_t t, uint32_t* bad_dev, void* stream);
 /* The same when the G entries are several verifiers' results over the same `columns` columns, one verifier after the other (G a multiple
- * of columns; 0 = G): bad[1] is the first failing COLUMN (entry index mod columns), bad[0] counts entries as before. */
+ * of columns, InvalidInput otherwise; 0 = G): bad[1] = min(bad[1], lowest failing COLUMN), the column of an entry being its index mod columns,
+ * wherever in the array the failures lie; bad[0] counts entries as before. */
 ShareErrorCode hbmpc_dev_check_double_share_c0_columns(hbmpc_ctx* ctx, const void* c0_t_dev, const uint32_t* degree_t_dev, const void* c0_2t_dev,
                                                        const uint32_t* degree_2t_dev, size_t G, size_t columns, size_t t, uint32_t* bad_dev,
                                                        void* stream);
@@ -441,8 +442,8 @@ ShareErrorCode hbmpc_dev_check_double_share_c0_columns(hbmpc_ctx* ctx, const voi
  * reference the network, here a transpose -- and the verifiers' verdicts, kept on the device:
  *   transpose       dst[b][c][r] = src[b][r][c] (strides in elements)
  *   check_degree    bad[0] += number of polynomials (coeffs[G][m], not trimmed) whose DensePolynomial::degree() is not
- *                   want_degree or whose status byte (nullable; from hbmpc_dev_batch_recover) is a failure; bad[1] =
- *                   min(bad[1], first such polynomial).  The caller zeroes bad[0] and sets bad[1] = 0xffffffff.
+ *                   want_degree or whose status byte (nullable; from hbmpc_dev_batch_recover) is a failure (above 1); bad[1] =
+ *                   min(bad[1], lowest such polynomial).  The caller zeroes bad[0] and sets bad[1] = 0xffffffff.
  *   check_double_share   the same for pairs: degree t, degree 2t and equal constant terms */
 ShareErrorCode hbmpc_dev_transpose(hbmpc_ctx* ctx, const void* src_dev, size_t rows, size_t cols, size_t src_row_stride, void* dst_dev,
                                    size_t dst_row_stride, size_t batch, size_t src_batch_stride, size_t dst_batch_stride, void* stream);
@@ -450,9 +451,13 @@ ShareErrorCode hbmpc_dev_check_degree(hbmpc_ctx* ctx, const void* coeffs_dev, co
                                       size_t want_degree, uint32_t* bad_dev, void* stream);
 /* The exact-degree verdict from the top coefficient alone: top_dev[G] = coefficient want_degree of each polynomial (what
  * hbmpc_dev_batch_recover_coeff_strided writes with k = want_degree), status_dev as above.  A polynomial of at most want_degree + 1
- * coefficients has that degree iff the coefficient is not zero (want_degree = 0: only the status counts).  Same bad[] as check_degree. */
+ * coefficients has that degree iff the coefficient is not zero (want_degree = 0: only the status counts).  Same bad[] as check_degree.
+ * _columns: the G entries are several verifiers' results over the same `columns` columns, one verifier after the other (G a multiple of
+ * columns, InvalidInput otherwise; 0 = one verifier): bad[1] = min(bad[1], lowest failing COLUMN = entry index mod columns). */
 ShareErrorCode hbmpc_dev_check_top_coeff(hbmpc_ctx* ctx, const void* top_dev, const uint8_t* status_dev, size_t G, size_t want_degree,
                                          uint32_t* bad_dev, void* stream);
+ShareErrorCode hbmpc_dev_check_top_coeff_columns(hbmpc_ctx* ctx, const void* top_dev, const uint8_t* status_dev, size_t G, size_t columns,
+                                                 size_t want_degree, uint32_t* bad_dev, void* stream);
 /* RanDouSha's verifier (ran_dou_sha/mod.rs:557-602) interpolates a polynomial through ALL n shares and asks three things of it: is its
  * degree exactly d, and its constant term.  hbmpc_[gl_]dev_interpolate_degree_check_strided answers them without the full interpolation:
  * the first d + 1 points (in id order) interpolate, every other point is a verify row (the points lie on a polynomial of degree <= d iff

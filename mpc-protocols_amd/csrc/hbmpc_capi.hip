@@ -2058,6 +2058,7 @@ static ShareErrorCode check_top_coeff_any(hbmpc_ctx* ctx, const void* top_dev, c
                                           void* stream, size_t columns) {
     if (!ctx) return InvalidInput;
     if (!bad_dev || (G && !top_dev) || want_degree > 65535) return fail(ctx, InvalidInput, "null buffer or bad degree");
+    if (columns && G % columns != 0) return fail(ctx, InvalidInput, "G must be a multiple of the number of columns");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = pick(ctx, stream);
     if (G) launch_check_top_coeff(is_gold(ctx) ? 1 : 4, (const uint64_t*)top_dev, status_dev, G, (int)want_degree, bad_dev, s, columns);
@@ -2067,6 +2068,10 @@ static ShareErrorCode check_top_coeff_any(hbmpc_ctx* ctx, const void* top_dev, c
 extern "C" ShareErrorCode hbmpc_dev_check_top_coeff(hbmpc_ctx* ctx, const void* top_dev, const uint8_t* status_dev, size_t G, size_t want_degree,
                                                     uint32_t* bad_dev, void* stream) {
     return check_top_coeff_any(ctx, top_dev, status_dev, G, want_degree, bad_dev, stream, 0);
+}
+extern "C" ShareErrorCode hbmpc_dev_check_top_coeff_columns(hbmpc_ctx* ctx, const void* top_dev, const uint8_t* status_dev, size_t G, size_t columns,
+                                                            size_t want_degree, uint32_t* bad_dev, void* stream) {
+    return check_top_coeff_any(ctx, top_dev, status_dev, G, want_degree, bad_dev, stream, columns);
 }
 extern "C" ShareErrorCode hbmpc_dev_check_double_share_sel(hbmpc_ctx* ctx, const void* sel_t_dev, const uint8_t* status_t_dev, const void* sel_2t_dev,
                                                            const uint8_t* status_2t_dev, size_t G, size_t columns, size_t t, uint32_t* bad_dev, void* stream) {
@@ -2090,7 +2095,7 @@ extern "C" ShareErrorCode hbmpc_dev_check_double_share(hbmpc_ctx* ctx, const voi
     return ShareSuccess;
 }
 // columns: 0, or the G entries are several verifiers' results for the same `columns` columns, one verifier after the other (G a multiple of it):
-// bad[1] is then the first failing COLUMN
+// bad[1] is then the lowest failing COLUMN
 extern "C" ShareErrorCode hbmpc_dev_check_double_share_c0_columns(hbmpc_ctx* ctx, const void* c0_t_dev, const uint32_t* degree_t_dev, const void* c0_2t_dev,
                                                                   const uint32_t* degree_2t_dev, size_t G, size_t columns, size_t t, uint32_t* bad_dev,
                                                                   void* stream) {

@@ -206,19 +206,33 @@ __device__ inline int layout_degree(const uint64_t* coeffs, int m) {
     }
     return 0;
 }
+// One wave's part of a verdict: bad[0] += its failing entries, bad[1] = min(bad[1], its lowest failing entry) -- or, with columns > 0
+// (several verifiers' results over the same columns, one verifier after the other), its lowest failing COLUMN g mod columns.  A wave that
+// holds the end of one verifier and the start of the next has its lowest column at a LATER lane than its first failure, so the minimum is
+// taken over all failing lanes.  Every lane of the wave calls this (no early return before it); a wave without a failure issues nothing,
+// one with some issues one atomicAdd and one atomicMin.
+__device__ __forceinline__ void verdict_commit(bool wrong, size_t g, size_t columns, uint32_t* __restrict__ bad) {
+    const unsigned long long mask = __ballot(wrong);
+    if (mask == 0) return;
+    uint32_t lowest = wrong ? (uint32_t)(columns ? g % columns : g) : 0xffffffffu;
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t other = __shfl_xor(lowest, off);
+        lowest = other < lowest ? other : lowest;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(bad, (uint32_t)__popcll(mask));
+        atomicMin(bad + 1, lowest);
+    }
+}
 // RanSha verifier (share_gen.rs:516-530): counts the chunks whose reconstruction failed (status not 0 / 1) or whose
-// polynomial does not have degree exactly `want`.  bad[0] += count, bad[1] = min(first bad chunk).
+// polynomial does not have degree exactly `want`.  bad[0] += count, bad[1] = min(bad[1], lowest failing chunk).
 template <int W>
 __global__ __launch_bounds__(256) void k_check_degree(const uint64_t* __restrict__ coeffs, const uint8_t* __restrict__ status, size_t G, int m,
                                                       int want, uint32_t* __restrict__ bad) {
     const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool wrong = false;
     if (g < G) wrong = (status && status[g] > 1) || layout_degree<W>(coeffs + g * (size_t)m * W, m) != want;
-    const unsigned long long mask = __ballot(wrong);
-    if (mask != 0 && (threadIdx.x & 63) == __ffsll((long long)mask) - 1) {
-        atomicAdd(bad, (uint32_t)__popcll(mask));
-        atomicMin(bad + 1, (uint32_t)g);
-    }
+    verdict_commit(wrong, g, 0, bad);
 }
 // The same verdict from the TOP coefficient alone (hbmpc_dev_batch_recover_coeff_strided with k = want): a polynomial of at most
 // `want` coefficients + 1 has degree exactly `want` > 0 iff that coefficient is not zero; want = 0 leaves the status test
@@ -233,11 +247,7 @@ __global__ __launch_bounds__(256) void k_check_top_coeff(const uint64_t* __restr
         for (int w = 0; w < W; ++w) any |= top[g * W + w];
         wrong = (status && status[g] > 1) || (want > 0 && any == 0);
     }
-    const unsigned long long mask = __ballot(wrong);
-    if (mask != 0 && (threadIdx.x & 63) == __ffsll((long long)mask) - 1) {
-        atomicAdd(bad, (uint32_t)__popcll(mask));
-        atomicMin(bad + 1, (uint32_t)(columns ? g % columns : g));  // several verifiers' columns in one launch: the column
-    }
+    verdict_commit(wrong, g, columns, bad);  // several verifiers' columns in one launch: the lowest failing column
 }
 // RanDouSha's verifier from the two kept coefficients of each interpolation (hbmpc_dev_interpolate_degree_check_strided): sel_t / sel_2t are
 // [G][2] = (constant term, coefficient t resp. 2t); a status above 1 says the points did not lie on a polynomial of that degree at all
@@ -254,11 +264,7 @@ __global__ __launch_bounds__(256) void k_check_double_sel(const uint64_t* __rest
         for (int w = 0; w < W; ++w) top_a |= a[W + w], top_b |= b[W + w], diff |= a[w] ^ b[w];
         wrong = st_t[g] > 1 || st_2t[g] > 1 || (t > 0 && (top_a == 0 || top_b == 0)) || diff != 0;
     }
-    const unsigned long long mask = __ballot(wrong);
-    if (mask != 0 && (threadIdx.x & 63) == __ffsll((long long)mask) - 1) {
-        atomicAdd(bad, (uint32_t)__popcll(mask));
-        atomicMin(bad + 1, (uint32_t)(columns ? g % columns : g));
-    }
+    verdict_commit(wrong, g, columns, bad);
 }
 // the same two coefficients and the verdict from a FULL interpolation (coeffs [G][m]): the form of the shapes the selective decode
 // does not cover
@@ -288,11 +294,7 @@ __global__ __launch_bounds__(256) void k_check_double(const uint64_t* __restrict
 #pragma unroll
         for (int w = 0; w < W; ++w) wrong |= a[w] != b[w];
     }
-    const unsigned long long mask = __ballot(wrong);
-    if (mask != 0 && (threadIdx.x & 63) == __ffsll((long long)mask) - 1) {
-        atomicAdd(bad, (uint32_t)__popcll(mask));
-        atomicMin(bad + 1, (uint32_t)g);
-    }
+    verdict_commit(wrong, g, 0, bad);
 }
 // the same tests from what the interpolation kernels leave when the coefficients are not needed: the constant terms c0[G] and the
 // degrees[G] of the two polynomials of every column (hbmpc_dev_batch_interpolate_c0)
@@ -307,11 +309,7 @@ __global__ __launch_bounds__(256) void k_check_double_c0(const uint64_t* __restr
 #pragma unroll
         for (int w = 0; w < W; ++w) wrong |= c0t[g * W + w] != c02t[g * W + w];
     }
-    const unsigned long long mask = __ballot(wrong);
-    if (mask != 0 && (threadIdx.x & 63) == __ffsll((long long)mask) - 1) {
-        atomicAdd(bad, (uint32_t)__popcll(mask));
-        atomicMin(bad + 1, (uint32_t)(g % columns));  // several verifiers' columns in one array: the column, not the chunk
-    }
+    verdict_commit(wrong, g, columns, bad);  // several verifiers' columns in one array: the lowest failing column, not the chunk
 }
 // c0[g] = coeffs[g][0] of chunk-major coefficient rows (the shapes without a fused kernel)
 template <int W>

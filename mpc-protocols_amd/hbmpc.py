@@ -453,6 +453,42 @@ class Engine:
         return self.L.hbmpc_dev_check_double_share(self.ctx, C.c_void_p(ct_d), C.c_void_p(c2t_d), C.c_size_t(G), C.c_size_t(m),
                                                    C.c_size_t(t), C.c_void_p(bad_d), C.c_void_p(stream))
 
+    def dev_check_top_coeff(self, top_d, status_d, G, want_degree, bad_d, columns=None, stream=0):
+        """columns=None: hbmpc_dev_check_top_coeff; a number: hbmpc_dev_check_top_coeff_columns"""
+        if columns is None:
+            return self.L.hbmpc_dev_check_top_coeff(self.ctx, C.c_void_p(top_d), C.c_void_p(status_d), C.c_size_t(G), C.c_size_t(want_degree),
+                                                    C.c_void_p(bad_d), C.c_void_p(stream))
+        return self.L.hbmpc_dev_check_top_coeff_columns(self.ctx, C.c_void_p(top_d), C.c_void_p(status_d), C.c_size_t(G), C.c_size_t(columns),
+                                                        C.c_size_t(want_degree), C.c_void_p(bad_d), C.c_void_p(stream))
+
+    def dev_check_double_share_sel(self, sel_t_d, st_t_d, sel_2t_d, st_2t_d, G, columns, t, bad_d, stream=0):
+        return self.L.hbmpc_dev_check_double_share_sel(self.ctx, C.c_void_p(sel_t_d), C.c_void_p(st_t_d), C.c_void_p(sel_2t_d), C.c_void_p(st_2t_d),
+                                                       C.c_size_t(G), C.c_size_t(columns), C.c_size_t(t), C.c_void_p(bad_d), C.c_void_p(stream))
+
+    def dev_check_double_share_c0(self, c0_t_d, deg_t_d, c0_2t_d, deg_2t_d, G, t, bad_d, columns=None, stream=0):
+        """columns=None: hbmpc_dev_check_double_share_c0; a number: hbmpc_dev_check_double_share_c0_columns"""
+        if columns is None:
+            return self.L.hbmpc_dev_check_double_share_c0(self.ctx, C.c_void_p(c0_t_d), C.c_void_p(deg_t_d), C.c_void_p(c0_2t_d), C.c_void_p(deg_2t_d),
+                                                          C.c_size_t(G), C.c_size_t(t), C.c_void_p(bad_d), C.c_void_p(stream))
+        return self.L.hbmpc_dev_check_double_share_c0_columns(self.ctx, C.c_void_p(c0_t_d), C.c_void_p(deg_t_d), C.c_void_p(c0_2t_d),
+                                                              C.c_void_p(deg_2t_d), C.c_size_t(G), C.c_size_t(columns), C.c_size_t(t),
+                                                              C.c_void_p(bad_d), C.c_void_p(stream))
+
+    def dev_batch_interpolate_c0(self, ids, evals_d, row_stride, G, n, tmp_coeffs_d, c0_d, degree_d, stream=0):
+        """what the RanDouSha verifier keeps of an interpolation through ALL len(ids) sender rows: c0[G], degree[G]; tmp_coeffs_d: G * len(ids)
+        elements, or 0 where the kernel writes just these (all n shares of an 8- or 16-point domain)"""
+        return self._f("dev_batch_interpolate_c0")(self.ctx, _p(_sz(ids)), C.c_size_t(len(ids)), C.c_void_p(evals_d), C.c_size_t(row_stride),
+                                                   C.c_size_t(G), C.c_size_t(n), C.c_void_p(tmp_coeffs_d), C.c_void_p(c0_d), C.c_void_p(degree_d),
+                                                   C.c_void_p(stream))
+
+    def dev_recover_check_degree_strided(self, sender_ids, evals_d, row_stride, G, n, t, ws_d, status_d, bad_d, groups=1, group_stride=0,
+                                         summary_d=0, stream=0):
+        """RanSha's verifier in one call: `groups` verifiers of G columns each; ws_d: max(groups G, G (t + 1)) elements, status_d: groups G bytes"""
+        return self._f("dev_recover_check_degree_strided")(self.ctx, _p(_sz(sender_ids)), C.c_size_t(len(sender_ids)), C.c_void_p(evals_d),
+                                                           C.c_size_t(row_stride), C.c_size_t(G), C.c_size_t(n), C.c_size_t(t), C.c_size_t(groups),
+                                                           C.c_size_t(group_stride), C.c_void_p(ws_d), C.c_void_p(status_d), C.c_void_p(summary_d),
+                                                           C.c_void_p(bad_d), C.c_void_p(stream))
+
     def dev_vandermonde_apply(self, x_d, G, n, d, y_d, stream=0):
         return self._f("dev_vandermonde_apply")(self.ctx, C.c_void_p(x_d), C.c_size_t(G), C.c_size_t(n),
                                                   C.c_size_t(d), C.c_void_p(y_d), C.c_void_p(stream))
