@@ -23,6 +23,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "fft_bounds.hpp"
 #include "fr_sat.hpp"
 #include "fr_u29.hpp"
 #include "kernels_recover.hpp"
@@ -30,41 +31,8 @@
 namespace hbmpc {
 
 // ---------------------------------------------------------------------------------------------
-// compile-time structure of the pruned FFT
+// the pruned FFT: its compile-time structure (bitrev_c, Bd, sub_k, fft_bd, fft_max_vb) is fft_bounds.hpp
 // ---------------------------------------------------------------------------------------------
-constexpr int bitrev_c(int log, int p) {
-    int r = 0;
-    for (int b = 0; b < log; ++b)
-        if (p & (1 << b)) r |= 1 << (log - 1 - b);
-    return r;
-}
-struct Bd {
-    int lbu;  // limb bound in units of 2^29 (0: element is identically zero)
-    int vb;   // value bound in units of r
-};
-constexpr int sub_k(int vb) {
-    return vb <= 1 ? 2 : vb <= 2 ? 4 : vb <= 4 ? 8 : vb <= 8 ? 16 : vb <= 16 ? 32 : vb <= 32 ? 64 : (1 << 20);
-}
-
-// bound of X[idx] after `stage` butterfly stages (stage 0 = bit-reversed inputs).  The code
-// generator below takes EXACTLY the same decisions (normalise u when lbu would pass 7, canonicalise
-// a lazy v before it is subtracted un-multiplied, normalise it before it is multiplied).
-constexpr Bd fft_bd(int LOG, int CNT, int LBU0, int VB0, int stage, int idx) {
-    if (stage == 0) return bitrev_c(LOG, idx) < CNT ? Bd{LBU0, VB0} : Bd{0, 0};
-    const int B = 1 << (stage - 1);
-    const int pos = idx & (2 * B - 1), k = pos & (B - 1);
-    const int iu = (idx & ~(2 * B - 1)) + k, iv = iu + B;
-    const bool upper = pos >= B;
-    const Bd u = fft_bd(LOG, CNT, LBU0, VB0, stage - 1, iu), v = fft_bd(LOG, CNT, LBU0, VB0, stage - 1, iv);
-    if (v.lbu == 0) return u;
-    // k != 0: t is a mulc output; k == 0: t is v itself when it is tight, else v canonicalised
-    const Bd t0 = k != 0 ? Bd{1, 2} : ((v.lbu == 1 && v.vb <= 2) ? v : Bd{1, 1});
-    const int K = sub_k(t0.vb);
-    if (u.lbu == 0) return upper ? Bd{2, K} : t0;
-    const Bd un = (u.lbu + 2 > 7) ? Bd{1, u.vb} : u;
-    return upper ? Bd{un.lbu + 2, un.vb + K} : Bd{un.lbu + t0.lbu, un.vb + t0.vb};
-}
-
 template <class F, int K>
 HB_DEV typename F::E sub_dispatch(const typename F::E& a, const typename F::E& b) {
     return F::template sub<K>(a, b);
@@ -167,16 +135,6 @@ HB_DEV void fft_pruned_sink(typename F::E (&X)[1 << LOG], const uint32_t* __rest
         fft_stages<F, LOG, CNT, LBU0, VB0>(X, tw, std::make_integer_sequence<int, LOG - 1>{});
         fft_last_stage_sink<F, LOG, CNT, LBU0, VB0>(X, tw, sink, std::make_integer_sequence<int, (1 << LOG) / 2>{});
     }
-}
-template <int LOG, int CNT, int LBU0, int VB0>
-constexpr int fft_max_vb() {
-    int m = 0;
-    for (int i = 0; i < (1 << LOG); ++i) {
-        const Bd b = fft_bd(LOG, CNT, LBU0, VB0, LOG, i);
-        if (b.vb > m) m = b.vb;
-        if (b.lbu > 7) return 1 << 20;
-    }
-    return m;
 }
 
 // ---------------------------------------------------------------------------------------------
