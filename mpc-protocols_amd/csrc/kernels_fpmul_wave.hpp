@@ -11,8 +11,14 @@
 //
 // The bytes of every buffer a caller can see are those of the separate launches (tests/test_gpu_pipelines.py): each value is
 // stored canonical, and a chunk that fails its verification opens to zero and is counted, exactly as there.
+//
+// The two opens and TruncPr's last step are wave_core.hpp's, as in k_mul_wave and k_truncpr_wave (the two halves of this kernel).
+// The staging, the products and the summary tail keep their own text here, word for word what wave_core.hpp's staging structs,
+// lane_product and finish_direct hold: composed of those, this kernel replayed as a graph measured 0.8 us slower at 64 elements
+// (0.0218 against 0.0211 ms; 0.3 us at 256), the compiler scheduling the longer body differently, and with these three written
+// out it is the earlier kernel's time again (profiles/wave_core.txt, section 4).  A change to one of them belongs in both places.
 #pragma once
-#include "kernels_recover.hpp"
+#include "wave_core.hpp"
 
 namespace hbmpc {
 
@@ -36,19 +42,19 @@ struct FpmulWaveArgs {
 };
 
 // LDS words of one workgroup (4 elements): per wave the senders' two values, the parties' operands, the products, the open
-// shares and the broadcast values; then pow2 | c0 | the table
+// shares and the broadcast values; then pow2 | c0 | the table.  Limbs sit at the 12-word stride of wave_core.hpp.
 struct FpmulWaveLds {
-    int per_wave, ysd, yse, ops, res, val, bc, consts, tab, total;
+    size_t per_wave, ysd, yse, ops, res, val, bc, consts, tab, total;
     __host__ __device__ FpmulWaveLds(int needed, int parties, int m, int tab_words) {
-        ysd = 0, yse = ysd + needed * 12;       // limbs (12-word stride)
-        ops = yse + needed * 12;                // [4 + m][party] canonical words: y, x, c, r_int, bits
-        res = ops + (4 + m) * parties * 8;      // [4][party] limbs
-        val = res + 4 * parties * 12;           // [party] limbs
-        bc = val + parties * 12;                // d, e (8 words each) | d R, e R (12 each) | the second open (8)
+        ysd = 0, yse = ysd + (size_t)needed * 12;     // limbs
+        ops = yse + (size_t)needed * 12;              // [4 + m][party] canonical words: y, x, c, r_int, bits
+        res = ops + (size_t)(4 + m) * parties * 8;    // [4][party] limbs
+        val = res + (size_t)4 * parties * 12;         // [party] limbs
+        bc = val + (size_t)parties * 12;              // d, e (8 words each) | d R, e R (12 each) | the second open (8)
         per_wave = bc + 16 + 24 + 8;
-        consts = 4 * per_wave;                  // [m + 1][12]: pow2 then c0
-        tab = consts + (m + 1) * 12;
-        total = tab + ((tab_words + 3) & ~3);
+        consts = 4 * per_wave;                        // [m + 1][12]: pow2 then c0
+        tab = consts + (size_t)(m + 1) * 12;
+        total = tab + (((size_t)tab_words + 3) & ~(size_t)3);
     }
 };
 
@@ -67,17 +73,6 @@ __global__ __launch_bounds__(256) void k_fpmul_wave(FpmulWaveArgs a) {
     uint32_t* W = lds + (size_t)wave * L.per_wave;
     uint32_t *ysd = W + L.ysd, *yse = W + L.yse, *ops = W + L.ops, *res = W + L.res, *val = W + L.val, *bc = W + L.bc;
     uint32_t *cst = lds + L.consts, *tab = lds + L.tab;
-
-    auto put_limbs = [&](uint32_t* dst, const E& v) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) dst[i] = v.l[i];
-    };
-    auto put_words = [&](uint32_t* dst, const E& canon) {
-        uint32_t w[8];
-        F::to_words(canon, w);
-        *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
-        *reinterpret_cast<uint4*>(dst + 4) = make_uint4(w[4], w[5], w[6], w[7]);
-    };
 
     // ---- every global load of the element, then the LDS writes -------------------------------------------------------------
     const int tq = tab_words >> 2;
@@ -115,8 +110,8 @@ __global__ __launch_bounds__(256) void k_fpmul_wave(FpmulWaveArgs a) {
     if ((int)threadIdx.x < ncw) cst[(threadIdx.x / 9) * 12 + threadIdx.x % 9] = cw;
     for (int w = threadIdx.x + 256; w < ncw; w += 256) cst[(w / 9) * 12 + w % 9] = w < a.m * 9 ? a.pow2[w] : a.c0[w - a.m * 9];
     if (lane < a.needed) {  // the shares Multiply opens (mul/multiplication.rs:417-426), canonical as k_beaver_open_pair stores them
-        put_limbs(ysd + lane * 12, F::canon_loose(F::template sub<2>(sa, sx)));
-        put_limbs(yse + lane * 12, F::canon_loose(F::template sub<2>(sb, sy)));
+        put_limbs<F>(ysd + lane * 12, F::canon_loose(F::template sub<2>(sa, sx)));
+        put_limbs<F>(yse + lane * 12, F::canon_loose(F::template sub<2>(sb, sy)));
     }
     if (lane < nops) {
         *reinterpret_cast<uint4*>(ops + lane * 8) = o0[0];
@@ -133,35 +128,9 @@ __global__ __launch_bounds__(256) void k_fpmul_wave(FpmulWaveArgs a) {
     }
     __syncthreads();
 
-    // a table row times the chunk's M values (LDS limbs), the products shared by 2^lk adjacent lanes (kernels_recover.hpp)
-    auto dot = [&](auto&& y_of, const uint32_t* row, int lk, int sidx) -> E {
-        return dot_shared<F>([&](int i) { return F::load_const(y_of(i)); }, row, M, lk, sidx);
-    };
-    // ---- the first open: a - x in lanes 0 .. 31, b - y in lanes 32 .. 63; row r of the table per lane -----------------------
-    // (r < nv verify rows; nv: P(0); nv + 1: P(0) R, what finalize_mul multiplies by)
-    {
-        const int h = lane >> 5, r = (lane & 31) >> a.lk1, sidx = lane & ((1 << a.lk1) - 1);
-        const uint32_t* ys = h ? yse : ysd;
-        bool bad = false;
-        E kept = F::zero();
-        if (r < nv + 2) {  // whole quads: the lanes that share a row are all in or all out
-            kept = dot([&](int i) { return ys + i * 12; }, tab + (size_t)r * M * 9, a.lk1, sidx);
-            if (r < nv) bad = !F::eq_canon(F::canon_loose(kept), F::load_const(ys + (M + r) * 12));
-        }
-        const unsigned long long vote = __ballot(bad);
-        const bool ok_d = (uint32_t)vote == 0, ok_e = (uint32_t)(vote >> 32) == 0, ok = h ? ok_e : ok_d;
-        if (r == nv && sidx == 0) {
-            const E v = ok ? F::canon_loose(kept) : F::zero();
-            put_words(bc + h * 8, v);
-            if (live) put_words(a.de_out + ((size_t)h * a.N + g) * 8, v);
-            if (live && h && a.status) a.status[a.N + g] = ok ? 0 : (uint8_t)DecodingError;
-        }
-        if (r == nv + 1 && sidx == 0) put_limbs(bc + 16 + h * 12, ok ? kept : F::zero());
-        if (live && lane == 0 && !(ok_d && ok_e)) {
-            atomicAdd(a.counters + 24, (ok_d ? 0u : 1u) + (ok_e ? 0u : 1u));
-            atomicMax(a.counters + 25, 0xffffffffu - (uint32_t)(ok_d ? a.N + g : g));
-        }
-    }
+    // ---- the first open (multiplication.rs:102-139): chunk g is the a - x of the element, chunk N + g its b - y; the a - x half's
+    // status byte is the second open's to write ----------------------------------------------------------------------------------
+    open_pair<F>(ysd, yse, tab, bc, a.lk1, nv, M, live, g, a.N, a.counters + 24, a.de_out, nullptr, a.status ? a.status + a.N : nullptr);
     __syncthreads();
 
     // ---- finalize_mul (multiplication.rs:57-100), r' (truncpr.rs:277-283), 2^m r_int: a product per lane ---------------------
@@ -184,7 +153,7 @@ __global__ __launch_bounds__(256) void k_fpmul_wave(FpmulWaveArgs a) {
             ++pending;
         }
         F::acc_fold(acc);
-        put_limbs(res + (q * P + p) * 12, F::acc_reduce(acc));
+        put_limbs<F>(res + (q * P + p) * 12, F::acc_reduce(acc));
     }
     __syncthreads();
     E zc = F::zero(), rd = F::zero();  // party `lane`'s z and r', kept for TruncPr's last step
@@ -196,54 +165,24 @@ __global__ __launch_bounds__(256) void k_fpmul_wave(FpmulWaveArgs a) {
         E o = F::add(zc, F::load_const(a.c1));
         o = F::add(o, F::load_const(res + (2 * P + p) * 12));
         o = F::canon_loose(F::add(o, rd));
-        put_limbs(val + p * 12, o);
+        put_limbs<F>(val + p * 12, o);
         if (live) {
             const size_t ip = (size_t)p * a.N + g;
-            put_words(a.z + ip * 8, zc);
-            put_words(a.r_dash + ip * 8, rd);
-            put_words(a.open_sh + ip * 8, o);
+            put_words<F>(a.z + ip * 8, zc);
+            put_words<F>(a.r_dash + ip * 8, rd);
+            put_words<F>(a.open_sh + ip * 8, o);
         }
     }
     __syncthreads();
 
     // ---- the second open (truncpr.rs:215) ---------------------------------------------------------------------------------
-    {
-        bool bad = false;
-        E kept = F::zero();
-        const int r = lane >> a.lk3, sidx = lane & ((1 << a.lk3) - 1);
-        if (r < nv + 1) {
-            kept = dot([&](int i) { return val + a.rows[i] * 12; }, tab + (size_t)r * M * 9, a.lk3, sidx);
-            if (r < nv) bad = !F::eq_canon(F::canon_loose(kept), F::load_const(val + row_of_lane(a.rows, M + r) * 12));
-        }
-        const bool ok = __ballot(bad) == 0;
-        if (r == nv && sidx == 0) {
-            const E v = ok ? F::canon_loose(kept) : F::zero();
-            put_words(bc + 40, v);
-            if (live) {
-                put_words(a.c_open + g * 8, v);
-                if (a.status) a.status[g] = ok ? 0 : (uint8_t)DecodingError;
-                if (!ok) {
-                    atomicAdd(a.counters, 1u);
-                    atomicMax(a.counters + 1, 0xffffffffu - (uint32_t)g);
-                }
-            }
-        }
-    }
+    open_single<F>(val, tab, bc + 40, a.lk3, nv, M, a.rows, live, g, a.counters, a.c_open, a.status);
     __syncthreads();
 
-    // ---- TruncPr's last step (truncpr.rs:216-220, fpmul/mod.rs:381-406): (z - ((c mod 2^m) - r')) 2^-m ------------------------
+    // ---- TruncPr's last step ---------------------------------------------------------------------------------------------------
     if (P <= 64) {
         if (lane < P) {
-            uint32_t w[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int lo_bit = 32 * q;
-                const uint32_t mask = a.mask_bits >= lo_bit + 32 ? 0xffffffffu : (a.mask_bits <= lo_bit ? 0u : ((1u << (a.mask_bits - lo_bit)) - 1u));
-                w[q] = bc[40 + q] & mask;
-            }
-            E tt = F::template sub<2>(rd, F::from_words(w));
-            tt = F::add(tt, zc);
-            const E o = F::mulc(tt, a.cinv);
+            const E o = truncpr_last<F>(bc + 40, a.mask_bits, rd, zc, a.cinv);
             if (live) F::store_lt2r(a.out + ((size_t)lane * a.N + g) * 8, o);
         }
     }

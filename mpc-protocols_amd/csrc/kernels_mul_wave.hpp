@@ -10,7 +10,7 @@
 // The bytes of every buffer a caller can see are those of the three launches (tests/test_gpu_mul.py): each value is stored
 // canonical, and a chunk that fails its verification opens to zero and is counted, exactly as there.
 #pragma once
-#include "kernels_recover.hpp"
+#include "wave_core.hpp"
 
 namespace hbmpc {
 
@@ -29,9 +29,7 @@ struct MulWaveArgs {
 };
 
 // LDS words of one workgroup (4 elements): per wave the senders' two values, the parties' operands, the two products and the
-// broadcast values; then the table.  Limbs sit at a 12-word stride: 16-byte aligned, and with one row per lane the 32 lanes of a
-// bank group start 12 banks apart -- at most 3 lanes to a bank (gcd(12, 32) = 4), against 8 at a 32-word stride and an
-// unaligned row at 9.  Every offset is a multiple of 4 words, so the uint4 stores of the operands and of d, e are aligned.
+// broadcast values; then the table.  Limbs sit at the 12-word stride of wave_core.hpp; every offset is a multiple of 4 words.
 struct MulWaveLds {
     size_t per_wave, ysd, yse, ops, res, bc, tab, total;
     __host__ __device__ MulWaveLds(int needed, int parties, int tab_words) {
@@ -61,27 +59,7 @@ __global__ __launch_bounds__(256) void k_mul_wave(MulWaveArgs a) {
     uint32_t *ysd = W + L.ysd, *yse = W + L.yse, *ops = W + L.ops, *res = W + L.res, *bc = W + L.bc;
     uint32_t* tab = lds + L.tab;
 
-    auto put_limbs = [&](uint32_t* dst, const E& v) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) dst[i] = v.l[i];
-    };
-    auto put_words = [&](uint32_t* dst, const E& canon) {
-        uint32_t w[8];
-        F::to_words(canon, w);
-        *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
-        *reinterpret_cast<uint4*>(dst + 4) = make_uint4(w[4], w[5], w[6], w[7]);
-    };
-
-    // ---- every global load of the element, then the LDS writes -------------------------------------------------------------
-    const int tq = tab_words >> 2;
-    uint4 t0 = make_uint4(0, 0, 0, 0), t1 = t0;
-    if ((int)threadIdx.x < tq) t0 = reinterpret_cast<const uint4*>(a.tab)[threadIdx.x];
-    if ((int)threadIdx.x + 256 < tq) t1 = reinterpret_cast<const uint4*>(a.tab)[threadIdx.x + 256];
-    E sa = F::zero(), sx = F::zero(), sb = F::zero(), sy = F::zero();
-    if (lane < a.needed) {
-        const size_t ip = (size_t)row_of_lane(a.rows, lane) * a.N + g;
-        sa = F::load(a.ta + ip * 8), sx = F::load(a.x + ip * 8), sb = F::load(a.tb + ip * 8), sy = F::load(a.y + ip * 8);
-    }
+    // ---- every global load of the element, then the LDS writes (wave_core.hpp) ---------------------------------------------------
     // operand item q of party p: 0 y, 1 x, 2 c
     const int nops = 3 * P;
     auto op_src = [&](int it) -> const uint32_t* {
@@ -89,84 +67,33 @@ __global__ __launch_bounds__(256) void k_mul_wave(MulWaveArgs a) {
         const uint32_t* base = q == 0 ? a.y : q == 1 ? a.x : a.tc;
         return base + ((size_t)p * a.N + g) * 8;
     };
-    uint4 o0[2] = {t0, t0}, o1[2] = {t0, t0};
-    if (lane < nops) {
-        const uint32_t* s = op_src(lane);
-        o0[0] = *reinterpret_cast<const uint4*>(s), o0[1] = *reinterpret_cast<const uint4*>(s + 4);
-    }
-    if (lane + 64 < nops) {
-        const uint32_t* s = op_src(lane + 64);
-        o1[0] = *reinterpret_cast<const uint4*>(s), o1[1] = *reinterpret_cast<const uint4*>(s + 4);
-    }
-    if ((int)threadIdx.x < tq) reinterpret_cast<uint4*>(tab)[threadIdx.x] = t0;
-    if ((int)threadIdx.x + 256 < tq) reinterpret_cast<uint4*>(tab)[threadIdx.x + 256] = t1;
-    for (int q = threadIdx.x + 512; q < tq; q += 256) reinterpret_cast<uint4*>(tab)[q] = reinterpret_cast<const uint4*>(a.tab)[q];
-    for (int w = (tq << 2) + threadIdx.x; w < tab_words; w += 256) tab[w] = a.tab[w];
-    if (lane < a.needed) {  // the shares Multiply opens (mul/multiplication.rs:417-426), canonical as k_beaver_open_pair stores them
-        put_limbs(ysd + lane * 12, F::canon_loose(F::template sub<2>(sa, sx)));
-        put_limbs(yse + lane * 12, F::canon_loose(F::template sub<2>(sb, sy)));
-    }
-    if (lane < nops) {
-        *reinterpret_cast<uint4*>(ops + lane * 8) = o0[0];
-        *reinterpret_cast<uint4*>(ops + lane * 8 + 4) = o0[1];
-    }
-    if (lane + 64 < nops) {
-        *reinterpret_cast<uint4*>(ops + (lane + 64) * 8) = o1[0];
-        *reinterpret_cast<uint4*>(ops + (lane + 64) * 8 + 4) = o1[1];
-    }
-    for (int it = lane + 128; it < nops; it += 64) {  // live from P = 43 on
-        const uint32_t* s = op_src(it);
-        *reinterpret_cast<uint4*>(ops + it * 8) = *reinterpret_cast<const uint4*>(s);
-        *reinterpret_cast<uint4*>(ops + it * 8 + 4) = *reinterpret_cast<const uint4*>(s + 4);
-    }
+    TableStage tabs;
+    PairStage<F> pair;
+    OperandStage opers;
+    tabs.load(a.tab, tab_words);
+    pair.load(a.ta, a.x, a.tb, a.y, a.rows, a.needed, a.N, g);
+    opers.load(op_src, nops);
+    tabs.store(tab, a.tab, tab_words);
+    pair.store(ysd, yse, a.needed);
+    opers.store(ops, op_src, nops);
     __syncthreads();
 
-    // ---- the open (multiplication.rs:102-139): a - x in lanes 0 .. 31, b - y in lanes 32 .. 63; row r of the table per lane ---
-    // (r < nv verify rows; nv: P(0); nv + 1: P(0) R, what finalize_mul multiplies by)
-    {
-        const int h = lane >> 5, r = (lane & 31) >> a.lk, sidx = lane & ((1 << a.lk) - 1);
-        const uint32_t* ys = h ? yse : ysd;
-        bool bad = false;
-        E kept = F::zero();
-        if (r < nv + 2) {  // whole quads: the lanes that share a row are all in or all out
-            kept = dot_shared<F>([&](int i) { return F::load_const(ys + i * 12); }, tab + (size_t)r * M * 9, M, a.lk, sidx);
-            if (r < nv) bad = !F::eq_canon(F::canon_loose(kept), F::load_const(ys + (M + r) * 12));
-        }
-        const unsigned long long vote = __ballot(bad);
-        const bool ok_d = (uint32_t)vote == 0, ok_e = (uint32_t)(vote >> 32) == 0, ok = h ? ok_e : ok_d;
-        if (r == nv && sidx == 0) {
-            const E v = ok ? F::canon_loose(kept) : F::zero();
-            put_words(bc + h * 8, v);
-            if (live) {
-                put_words(a.de_out + ((size_t)h * a.N + g) * 8, v);
-                if (a.status) a.status[(size_t)h * a.N + g] = ok ? 0 : (uint8_t)DecodingError;
-            }
-        }
-        if (r == nv + 1 && sidx == 0) put_limbs(bc + 16 + h * 12, ok ? kept : F::zero());
-        if (live && lane == 0 && !(ok_d && ok_e)) {  // chunk g is the a - x of the element, chunk N + g its b - y
-            atomicAdd(a.counters, (ok_d ? 0u : 1u) + (ok_e ? 0u : 1u));
-            atomicMax(a.counters + 1, 0xffffffffu - (uint32_t)(ok_d ? a.N + g : g));
-        }
-    }
+    // ---- the open (multiplication.rs:102-139): chunk g is the a - x of the element, chunk N + g its b - y ------------------------
+    open_pair<F>(ysd, yse, tab, bc, a.lk, nv, M, live, g, a.N, a.counters, a.de_out, a.status, a.status ? a.status + a.N : nullptr);
     __syncthreads();
 
     // ---- finalize_mul (multiplication.rs:57-100): a product per lane -----------------------------------------------------------
     //   q = 0: (e + y_p) d R    1: x_p e R
     for (int task = lane; task < 2 * P; task += 64) {
         const int q = task / P, p = task - q * P;
-        typename F::Acc acc;
-        F::acc_zero(acc);
-        E v = F::load(ops + (q * P + p) * 8);
-        if (q == 0) v = F::normalize(F::add(v, F::load(bc + 8)));
-        F::acc_mac(acc, v, bc + 16 + q * 12);
-        F::acc_fold(acc);
-        put_limbs(res + (q * P + p) * 12, F::acc_reduce(acc));
+        lane_product<F>(res + (q * P + p) * 12, ops + (q * P + p) * 8, 0, bc + 16 + q * 12, 1,
+                        [&](const E& v) { return q == 0 ? F::normalize(F::add(v, F::load(bc + 8))) : v; });
     }
     __syncthreads();
     for (int p = lane; p < P; p += 64) {  // z_p = c_p - both
         E acc = F::template sub<4>(F::load(ops + (2 * P + p) * 8), F::load_const(res + p * 12));
         acc = F::template sub<4>(acc, F::load_const(res + (P + p) * 12));
-        if (live) put_words(a.z + ((size_t)p * a.N + g) * 8, F::canon_loose(acc));
+        if (live) put_words<F>(a.z + ((size_t)p * a.N + g) * 8, F::canon_loose(acc));
     }
 
     // ---- the summary: the last workgroup turns the counters into it and leaves the counters at zero ----------------------------

@@ -13,7 +13,7 @@
 //
 // Every buffer a caller can see gets the bytes of the separate launches (tests/test_gpu_prandbit_parties.py).
 #pragma once
-#include "kernels_recover.hpp"
+#include "wave_core.hpp"
 #include "kernels_riss.hpp"
 #include "prandbit_route.hpp"
 
@@ -145,35 +145,26 @@ __global__ __launch_bounds__(256) void k_prandbit_wg(PRandBitWgArgs a) {
             }
         }
         rp = F::canon_loose(accF.reduce(a.red));
-        uint32_t w[8];
-        F::to_words(rp, w);
-        *reinterpret_cast<uint4*>(a.r_p + oi * 8) = make_uint4(w[0], w[1], w[2], w[3]);
-        *reinterpret_cast<uint4*>(a.r_p + oi * 8 + 4) = make_uint4(w[4], w[5], w[6], w[7]);
+        put_words<F>(a.r_p + oi * 8, rp);
         if constexpr (BIT) {
             a.r_2[oi] = (uint8_t)a2;
             const GE rq = accG.reduce(nullptr);
             const GE v = Gold::add(rq, Gold::e(a.b_q[oi]));  // r + b, as the element-wise add computes it
             a.r_q[oi] = Gold::u(rq);
             a.rb[oi] = Gold::u(v);
-            X[(p * M + k) * 2] = v.l[0], X[(p * M + k) * 2 + 1] = v.l[1];
+            put_limbs<Gold>(X + (p * M + k) * 2, v);
         }
     }
     if constexpr (!BIT) return;
     __syncthreads();
 
-    auto gdot = [&](auto&& value_of, const uint32_t* row) -> GE {
-        Gold::Acc acc;
-        Gold::acc_zero(acc);
-        for (int i = 0; i < M; ++i) Gold::acc_mac(acc, value_of(i), row + i * 2);
-        return Gold::acc_reduce(acc);
-    };
-    auto put = [&](uint32_t* dst, const GE& v) { dst[0] = v.l[0], dst[1] = v.l[1]; };
+    auto gdot = [&](auto&& value_of, const uint32_t* row) -> GE { return dot_rows<Gold>(value_of, row, M, 0, 0); };  // a lane per row
 
     // ---- BatchRecon (degree t) of r + b over Goldilocks, as k_randbit_wg's open runs it (batch_recon.rs:157-165, :384-391, :457-467) -------
     // the encode: a lane per (party q, recipient j): y = sum_k alpha_j^k x_q[k]
     for (int it = tid; it < n * n; it += 256) {
         const int q = it / n, j = it - q * n;
-        put(Yl + it * 2, gdot([&](int i) { return Gold::load_const(X + (q * M + i) * 2); }, vmat + (size_t)j * M * 2));
+        put_limbs<Gold>(Yl + it * 2, gdot([&](int i) { return Gold::load_const(X + (q * M + i) * 2); }, vmat + (size_t)j * M * 2));
     }
     __syncthreads();
     // the EvalBatch arm: recipient j opens its value from senders 0 .. 2t: t verify rows and the P(0) row
@@ -188,7 +179,7 @@ __global__ __launch_bounds__(256) void k_prandbit_wg(PRandBitWgArgs a) {
         __syncthreads();
         if (mine && r == nv) {
             const bool ok = flags[j] == 0;
-            put(Zl + j * 2, ok ? kept : Gold::zero());
+            put_limbs<Gold>(Zl + j * 2, ok ? kept : Gold::zero());
             const size_t g = (size_t)j * G + c;
             if (j > 0) a.rstatus[g] = ok ? 0 : (uint8_t)DecodingError;  // recipient 0's is rewritten by the second decode
             if (!ok) {
@@ -212,7 +203,7 @@ __global__ __launch_bounds__(256) void k_prandbit_wg(PRandBitWgArgs a) {
             const bool ok = flags[n] == 0;
             if (r >= nv) {
                 const GE o = ok ? kept : Gold::zero();
-                put(Ol + (r - nv) * 2, o);
+                put_limbs<Gold>(Ol + (r - nv) * 2, o);
                 a.opened[c * M + (r - nv)] = Gold::u(o);
             }
             if (r == nv) {
@@ -233,29 +224,8 @@ __global__ __launch_bounds__(256) void k_prandbit_wg(PRandBitWgArgs a) {
         a.b_2[oi] = (uint8_t)a2 ^ (uint8_t)(w[0] & 1u);
     }
 
-    // ---- the summaries: the last workgroup turns the counters into them and leaves the counters at zero (k_randbit_wg) ---------------------
-    __syncthreads();
-    if (tid != 0) return;
-    __threadfence();
-    const unsigned nblocks = gridDim.x, sub = blockIdx.x % DIRECT_FAN, quota = nblocks / DIRECT_FAN + (sub < nblocks % DIRECT_FAN ? 1u : 0u);
-    if (atomicAdd(a.counters + 8 + sub, 1u) != quota - 1) return;
-    const unsigned groups = nblocks < DIRECT_FAN ? nblocks : DIRECT_FAN;
-    if (atomicAdd(a.counters + 3, 1u) != groups - 1) return;
-    __threadfence();
-#pragma unroll
-    for (unsigned q = 0; q < DIRECT_FAN; ++q) store_handoff(a.counters + 8 + q, 0u);
-    auto summarise = [&](uint32_t* summary, int slot) {
-        const uint32_t f = load_handoff(a.counters + slot), l = load_handoff(a.counters + slot + 1);
-        summary[0] = f, summary[1] = f;
-        summary[2] = f ? 0xffffffffu - l : 0xffffffffu;
-        summary[3] = f ? (uint32_t)DecodingError : 0u;
-        store_handoff(a.counters + slot, 0u);
-        store_handoff(a.counters + slot + 1, 0u);
-    };
-    summarise(a.sm_first, 24);
-    summarise(a.sm, 0);
-    store_handoff(a.counters + 2, 0u);
-    store_handoff(a.counters + 3, 0u);
+    // ---- the summaries: the last workgroup turns the counters into them and leaves the counters at zero ------------------------------------
+    finish_direct(a.counters, {{a.sm_first, 24}, {a.sm, 0}});
 }
 
 }  // namespace hbmpc

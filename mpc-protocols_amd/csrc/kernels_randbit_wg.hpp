@@ -13,7 +13,7 @@
 //
 // Every buffer a caller can see gets the bytes of the nine launches (tests/test_gpu_randbit_parties.py).
 #pragma once
-#include "kernels_recover.hpp"
+#include "wave_core.hpp"
 #include "kernels_sqrt.hpp"
 
 namespace hbmpc {
@@ -59,30 +59,6 @@ __global__ __launch_bounds__(256) void k_randbit_wg(RandBitWgArgs a) {
     const RandBitWgLds L(n, t, LS, NL);
     uint32_t *X = lds + L.X, *Yl = lds + L.Y, *Zl = lds + L.Z, *Ol = lds + L.O, *Sl = lds + L.S, *flags = lds + L.flags, *pst = lds + L.pst;
     uint32_t *vmat = lds + L.vmat, *tab = lds + L.tab;
-    auto put_limbs = [&](uint32_t* dst, const E& v) {
-#pragma unroll
-        for (int i = 0; i < NL; ++i) dst[i] = v.l[i];
-    };
-    auto put_words = [&](uint32_t* dst, const E& canon) {  // canonical value -> the stored form
-        if constexpr (SHARE) {
-            uint32_t w[8];
-            F::to_words(canon, w);
-            *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
-            *reinterpret_cast<uint4*>(dst + 4) = make_uint4(w[4], w[5], w[6], w[7]);
-        } else {
-            F::store_lt2r(dst, canon);
-        }
-    };
-    auto dot = [&](auto&& value_of, const uint32_t* row, int lk, int sidx) -> E {
-        if constexpr (SHARE) {
-            return dot_shared<F>(value_of, row, M, lk, sidx);
-        } else {
-            typename F::Acc acc;
-            F::acc_zero(acc);
-            for (int i = 0; i < M; ++i) F::acc_mac(acc, value_of(i), row + i * NL);
-            return F::acc_reduce(acc);
-        }
-    };
     // lanes that share a row's products: as many as leave every row of a step inside the workgroup's one pass
     auto share_log = [&](int rows) {
         int lk = 0;
@@ -98,8 +74,8 @@ __global__ __launch_bounds__(256) void k_randbit_wg(RandBitWgArgs a) {
         // the encode (batch_recon.rs:157-165): a lane per (chunk, party p, recipient j): y = sum_k alpha_j^k x_p[k]
         for (int it = tid; it < W * n * n; it += 256) {
             const int wp = it / n, j = it - wp * n;  // wp = w n + p
-            const E y = F::canon_loose(dot([&](int k) { return F::load_const(X + (wp * M + k) * LS); }, vmat + (size_t)j * M * NL, 0, 0));
-            put_limbs(Yl + (wp * n + j) * LS, y);
+            const E y = F::canon_loose(dot_rows<F>([&](int k) { return F::load_const(X + (wp * M + k) * LS); }, vmat + (size_t)j * M * NL, M, 0, 0));
+            put_limbs<F>(Yl + (wp * n + j) * LS, y);
         }
         __syncthreads();
         // the EvalBatch arm (:384-391): recipient j opens its value from senders 0 .. 2t: t verify rows and the P(0) row
@@ -110,14 +86,14 @@ __global__ __launch_bounds__(256) void k_randbit_wg(RandBitWgArgs a) {
             const bool mine = q < W * n * (nv + 1);
             E kept = F::zero();
             if (mine) {
-                kept = dot([&](int i) { return F::load_const(Yl + ((w * n + i) * n + j) * LS); }, tab + (size_t)(r < nv ? r : nv) * M * NL, lk, sidx);
+                kept = dot_rows<F>([&](int i) { return F::load_const(Yl + ((w * n + i) * n + j) * LS); }, tab + (size_t)(r < nv ? r : nv) * M * NL, M, lk, sidx);
                 if (r < nv && sidx == 0 && !F::eq_canon(F::canon_loose(kept), F::load_const(Yl + ((w * n + M + r) * n + j) * LS)))
                     flags[w * (n + 1) + j] = 1;
             }
             __syncthreads();
             if (mine && r == nv && sidx == 0) {
                 const bool ok = flags[w * (n + 1) + j] == 0;
-                put_limbs(Zl + wj * LS, ok ? F::canon_loose(kept) : F::zero());
+                put_limbs<F>(Zl + wj * LS, ok ? F::canon_loose(kept) : F::zero());
                 const size_t g = (size_t)j * G + (size_t)w * Gsq + c;
                 if (j > 0) rst[g] = ok ? 0 : (uint8_t)DecodingError;  // recipient 0's is rewritten by the second decode
                 if (!ok) {
@@ -135,7 +111,7 @@ __global__ __launch_bounds__(256) void k_randbit_wg(RandBitWgArgs a) {
             const bool mine = q < W * (nv + M);
             E kept = F::zero();
             if (mine) {
-                kept = dot([&](int i) { return F::load_const(Zl + (w * n + i) * LS); }, tab + (size_t)r * M * NL, lk, sidx);
+                kept = dot_rows<F>([&](int i) { return F::load_const(Zl + (w * n + i) * LS); }, tab + (size_t)r * M * NL, M, lk, sidx);
                 if (r < nv && sidx == 0 && !F::eq_canon(F::canon_loose(kept), F::load_const(Zl + (w * n + M + r) * LS))) flags[w * (n + 1) + n] = 1;
             }
             __syncthreads();
@@ -144,8 +120,8 @@ __global__ __launch_bounds__(256) void k_randbit_wg(RandBitWgArgs a) {
                 const size_t g = (size_t)w * Gsq + c;
                 if (r >= nv) {
                     const E o = ok ? F::canon_loose(kept) : F::zero();
-                    put_limbs(Ol + (w * M + (r - nv)) * LS, o);
-                    put_words(opened + (g * M + (r - nv)) * EW, o);
+                    put_limbs<F>(Ol + (w * M + (r - nv)) * LS, o);
+                    put_words<F>(opened + (g * M + (r - nv)) * EW, o);
                 }
                 if (r == nv) {
                     rst[g] = ok ? 0 : (uint8_t)DecodingError;
@@ -171,11 +147,11 @@ __global__ __launch_bounds__(256) void k_randbit_wg(RandBitWgArgs a) {
         va = F::load(a.a + e * EW), vtc = F::load(a.tc + e * EW);
         const E d_sh = F::canon_loose(F::template sub<2>(F::load(a.ta + e * EW), va));
         const E e_sh = F::canon_loose(F::template sub<2>(F::load(a.tb + e * EW), va));
-        put_limbs(X + (pk_p * M + pk_k) * LS, d_sh);
-        put_limbs(X + ((n + pk_p) * M + pk_k) * LS, e_sh);
+        put_limbs<F>(X + (pk_p * M + pk_k) * LS, d_sh);
+        put_limbs<F>(X + ((n + pk_p) * M + pk_k) * LS, e_sh);
         const size_t o = (size_t)pk_p * 2 * a.N + c * M + pk_k;
-        put_words(a.desh + o * EW, d_sh);
-        put_words(a.desh + (o + a.N) * EW, e_sh);
+        put_words<F>(a.desh + o * EW, d_sh);
+        put_words<F>(a.desh + (o + a.N) * EW, e_sh);
     }
     __syncthreads();
 
@@ -189,8 +165,8 @@ __global__ __launch_bounds__(256) void k_randbit_wg(RandBitWgArgs a) {
         const E dey = F::mont(F::add(ev, va), dm);
         const E ex = F::mont(va, em);
         const E s = F::canon_loose(F::template sub<4>(F::template sub<4>(vtc, dey), ex));
-        put_limbs(X + (pk_p * M + pk_k) * LS, s);
-        put_words(a.sq + e * EW, s);
+        put_limbs<F>(X + (pk_p * M + pk_k) * LS, s);
+        put_words<F>(a.sq + e * EW, s);
     }
     __syncthreads();
 
@@ -213,7 +189,7 @@ __global__ __launch_bounds__(256) void k_randbit_wg(RandBitWgArgs a) {
             atomicAdd(&a.rb->n_failed, 1u);
         } else {
             const uint32_t Ee = (0u - (Lg >> 1)) & 0x7fffffffu;
-            put_limbs(Sl + tid * LS, sq_mulc<F>(sq_mul<F>(u, omega_pow<F>(a.st, 0u - (Lg + Ee))), a.st.half));
+            put_limbs<F>(Sl + tid * LS, sq_mulc<F>(sq_mul<F>(u, omega_pow<F>(a.st, 0u - (Lg + Ee))), a.st.half));
         }
     }
     __syncthreads();
@@ -227,7 +203,10 @@ __global__ __launch_bounds__(256) void k_randbit_wg(RandBitWgArgs a) {
         }
     }
 
-    // ---- the summaries: the last workgroup turns the counters into them and leaves the counters at zero (k_triplegen_wg) ----------------
+    // ---- the summaries: the last workgroup turns the counters into them and leaves the counters at zero.  finish_direct
+    // (kernels_recover.hpp) written out: with it this kernel, 85 KB of text, measured 1.5 % slower at 1024 chunks over Fr and no slower
+    // at 1 or 4096 -- where the code lands, not what it does -- and with its own tail it is the earlier kernel instruction for
+    // instruction (profiles/wave_core.txt, section 4) -----------------------------------------------------------------------------------
     __syncthreads();
     if (tid != 0) return;
     __threadfence();

@@ -113,8 +113,16 @@ HB_DEV void count_failures(bool bad, size_t g, uint32_t* counters) {
 // every thread of every block, at the end of a direct kernel.  The ticket is two-level (16 sub-tickets in counters[8..24),
 // then counters[3]): thousands of blocks taking one ticket word serialise on it -- 2048 blocks of the wave-per-chunk
 // kernel added 11 us to a 20 us call.
+// A kernel that runs several decodes (the one-launch protocol kernels) counts each in a pair of its own -- (slot, slot + 1) used
+// as ([0], [1]) above, slot 0 or from 24 on -- and hands every pair with its summary (null: not wanted) to this one tail, which
+// leaves the pairs, the tickets and counters[0..4) at zero for the next call on the stream.
 constexpr unsigned DIRECT_FAN = 16;
-HB_DEV void finish_direct(uint32_t* counters, uint32_t* summary) {
+struct SummarySlot {
+    uint32_t* summary;
+    int slot;
+};
+template <int K>
+HB_DEV void finish_direct(uint32_t* counters, const SummarySlot (&s)[K]) {
     __syncthreads();
     if (threadIdx.x != 0) return;
     const unsigned nblocks = gridDim.x * gridDim.y, b = blockIdx.y * gridDim.x + blockIdx.x;
@@ -126,14 +134,28 @@ HB_DEV void finish_direct(uint32_t* counters, uint32_t* summary) {
     __threadfence();  // acquire: every other block's counts before the summary is read
 #pragma unroll
     for (unsigned k = 0; k < DIRECT_FAN; ++k) store_handoff(counters + 8 + k, 0u);
-    const uint32_t failed = load_handoff(counters), low = load_handoff(counters + 1);
-    if (summary) {
-        summary[0] = failed, summary[1] = failed;
-        summary[2] = failed ? 0xffffffffu - low : 0xffffffffu;
-        summary[3] = failed ? (uint32_t)DecodingError : 0u;
+    uint32_t failed[K], low[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) failed[i] = load_handoff(counters + s[i].slot), low[i] = load_handoff(counters + s[i].slot + 1);
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        uint32_t* summary = s[i].summary;
+        if (summary) {
+            summary[0] = failed[i], summary[1] = failed[i];
+            summary[2] = failed[i] ? 0xffffffffu - low[i] : 0xffffffffu;
+            summary[3] = failed[i] ? (uint32_t)DecodingError : 0u;
+        }
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) store_handoff(counters + k, 0u);
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        if (s[i].slot >= 4) store_handoff(counters + s[i].slot, 0u), store_handoff(counters + s[i].slot + 1, 0u);
+    }
+}
+HB_DEV void finish_direct(uint32_t* counters, uint32_t* summary) {
+    const SummarySlot one[1] = {{summary, 0}};
+    finish_direct(counters, one);
 }
 
 // M = d + 1 known at compile time: the chunk's m interpolation inputs live in registers (9 M VGPRs).

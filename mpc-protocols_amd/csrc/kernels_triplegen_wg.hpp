@@ -11,7 +11,7 @@
 //
 // Every buffer a caller can see gets the bytes of the separate launches (tests/test_gpu_pipelines.py).
 #pragma once
-#include "kernels_recover.hpp"
+#include "wave_core.hpp"
 
 namespace hbmpc {
 
@@ -51,30 +51,6 @@ __global__ __launch_bounds__(256) void k_triplegen_wg(TripleGenWgArgs a) {
     const size_t g = blockIdx.x;
     const TripleGenWgLds L(n, t, LS, NL);
     uint32_t *X = lds + L.X, *Yl = lds + L.Y, *Zl = lds + L.Z, *Ol = lds + L.O, *flags = lds + L.flags, *vmat = lds + L.vmat, *tab = lds + L.tab;
-    auto put_limbs = [&](uint32_t* dst, const E& v) {
-#pragma unroll
-        for (int i = 0; i < NL; ++i) dst[i] = v.l[i];
-    };
-    auto put_words = [&](uint32_t* dst, const E& canon) {  // canonical value -> the stored form
-        if constexpr (SHARE) {
-            uint32_t w[8];
-            F::to_words(canon, w);
-            *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
-            *reinterpret_cast<uint4*>(dst + 4) = make_uint4(w[4], w[5], w[6], w[7]);
-        } else {
-            F::store_lt2r(dst, canon);
-        }
-    };
-    auto dot = [&](auto&& value_of, const uint32_t* row, int lk, int sidx) -> E {
-        if constexpr (SHARE) {
-            return dot_shared<F>(value_of, row, M, lk, sidx);
-        } else {
-            typename F::Acc acc;
-            F::acc_zero(acc);
-            for (int i = 0; i < M; ++i) F::acc_mac(acc, value_of(i), row + i * NL);
-            return F::acc_reduce(acc);
-        }
-    };
     constexpr int LK1 = SHARE ? 1 : 0;
 
     // ---- loads: a lane per (party, triple of the chunk); the tables by everyone ----------------------------------------------------
@@ -89,7 +65,7 @@ __global__ __launch_bounds__(256) void k_triplegen_wg(TripleGenWgArgs a) {
     // [ab - r]_2t = a_i b_i - r2t_i  (triple_generation.rs:333-340), canonical as k_triple_local stores it
     if (pk) {
         const E am = F::mulc(va, a.r2);
-        put_limbs(X + (pk_p * M + pk_k) * LS, F::canon_loose(F::template sub<2>(F::mont(vb, am), vr)));
+        put_limbs<F>(X + (pk_p * M + pk_k) * LS, F::canon_loose(F::template sub<2>(F::mont(vb, am), vr)));
     }
     __syncthreads();
 
@@ -97,9 +73,9 @@ __global__ __launch_bounds__(256) void k_triplegen_wg(TripleGenWgArgs a) {
     {
         const int p = tid / n, j = tid - p * n;
         if (tid < n * n) {
-            const E y = F::canon_loose(dot([&](int k) { return F::load_const(X + (p * M + k) * LS); }, vmat + (size_t)j * M * NL, 0, 0));
-            put_limbs(Yl + (p * n + j) * LS, y);
-            put_words(a.Y + (((size_t)p * n + j) * a.G + g) * EW, y);
+            const E y = F::canon_loose(dot_rows<F>([&](int k) { return F::load_const(X + (p * M + k) * LS); }, vmat + (size_t)j * M * NL, M, 0, 0));
+            put_limbs<F>(Yl + (p * n + j) * LS, y);
+            put_words<F>(a.Y + (((size_t)p * n + j) * a.G + g) * EW, y);
         }
     }
     __syncthreads();
@@ -110,15 +86,15 @@ __global__ __launch_bounds__(256) void k_triplegen_wg(TripleGenWgArgs a) {
         const int q = tid >> LK1, sidx = tid & ((1 << LK1) - 1), j = q / (nv + 1), r = q - j * (nv + 1);
         E kept = F::zero();
         if (q < n * (nv + 1)) {
-            kept = dot([&](int i) { return F::load_const(Yl + (i * n + j) * LS); }, tab + (size_t)(r < nv ? r : nv) * M * NL, LK1, sidx);
+            kept = dot_rows<F>([&](int i) { return F::load_const(Yl + (i * n + j) * LS); }, tab + (size_t)(r < nv ? r : nv) * M * NL, M, LK1, sidx);
             if (r < nv && sidx == 0 && !F::eq_canon(F::canon_loose(kept), F::load_const(Yl + ((M + r) * n + j) * LS))) flags[j] = 1;
         }
         __syncthreads();
         if (q < n * (nv + 1) && r == nv && sidx == 0) {
             const bool ok = flags[j] == 0;
             const E z = ok ? F::canon_loose(kept) : F::zero();
-            put_limbs(Zl + j * LS, z);
-            put_words(a.Z + ((size_t)j * a.G + g) * EW, z);
+            put_limbs<F>(Zl + j * LS, z);
+            put_words<F>(a.Z + ((size_t)j * a.G + g) * EW, z);
             if (a.status && j > 0) a.status[(size_t)j * a.G + g] = ok ? 0 : (uint8_t)DecodingError;  // recipient 0's is rewritten by the second decode
             if (!ok) {
                 atomicAdd(a.counters + 24, 1u);
@@ -135,15 +111,15 @@ __global__ __launch_bounds__(256) void k_triplegen_wg(TripleGenWgArgs a) {
         const int r = tid >> lk, sidx = tid & ((1 << lk) - 1);
         E kept = F::zero();
         if (r < nv + M) {
-            kept = dot([&](int i) { return F::load_const(Zl + i * LS); }, tab + (size_t)r * M * NL, lk, sidx);
+            kept = dot_rows<F>([&](int i) { return F::load_const(Zl + i * LS); }, tab + (size_t)r * M * NL, M, lk, sidx);
             if (r < nv && sidx == 0 && !F::eq_canon(F::canon_loose(kept), F::load_const(Zl + (M + r) * LS))) flags[n] = 1;
         }
         __syncthreads();
         const bool ok = flags[n] == 0;
         if (r >= nv && r < nv + M && sidx == 0) {
             const E o = ok ? F::canon_loose(kept) : F::zero();
-            put_limbs(Ol + (r - nv) * LS, o);
-            put_words(a.opened + (g * M + (r - nv)) * EW, o);
+            put_limbs<F>(Ol + (r - nv) * LS, o);
+            put_words<F>(a.opened + (g * M + (r - nv)) * EW, o);
         }
         if (tid == 0) {
             if (a.status) a.status[g] = ok ? 0 : (uint8_t)DecodingError;
@@ -159,32 +135,7 @@ __global__ __launch_bounds__(256) void k_triplegen_wg(TripleGenWgArgs a) {
     if (pk) F::store_loose(a.c + e * EW, F::add(vrt, F::load_const(Ol + pk_k * LS)));
 
     // ---- the summaries: the last workgroup turns the counters into them and leaves the counters at zero ------------------------------
-    __syncthreads();
-    if (tid != 0) return;
-    __threadfence();
-    const unsigned nblocks = gridDim.x, sub = blockIdx.x % DIRECT_FAN, quota = nblocks / DIRECT_FAN + (sub < nblocks % DIRECT_FAN ? 1u : 0u);
-    if (atomicAdd(a.counters + 8 + sub, 1u) != quota - 1) return;
-    const unsigned groups = nblocks < DIRECT_FAN ? nblocks : DIRECT_FAN;
-    if (atomicAdd(a.counters + 3, 1u) != groups - 1) return;
-    __threadfence();
-#pragma unroll
-    for (unsigned k = 0; k < DIRECT_FAN; ++k) store_handoff(a.counters + 8 + k, 0u);
-    const uint32_t f1 = load_handoff(a.counters + 24), l1 = load_handoff(a.counters + 25);
-    const uint32_t f2 = load_handoff(a.counters), l2 = load_handoff(a.counters + 1);
-    if (a.summary_first) {
-        a.summary_first[0] = f1, a.summary_first[1] = f1;
-        a.summary_first[2] = f1 ? 0xffffffffu - l1 : 0xffffffffu;
-        a.summary_first[3] = f1 ? (uint32_t)DecodingError : 0u;
-    }
-    if (a.summary) {
-        a.summary[0] = f2, a.summary[1] = f2;
-        a.summary[2] = f2 ? 0xffffffffu - l2 : 0xffffffffu;
-        a.summary[3] = f2 ? (uint32_t)DecodingError : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) store_handoff(a.counters + k, 0u);
-    store_handoff(a.counters + 24, 0u);
-    store_handoff(a.counters + 25, 0u);
+    finish_direct(a.counters, {{a.summary_first, 24}, {a.summary, 0}});
 }
 
 }  // namespace hbmpc

@@ -400,6 +400,23 @@ def test_tampered_shares(pkg, engines, stream, n, t):
     both_forms_match(engines, pkg, stream, n, t, contrib, b_q, m)
 
 
+def test_counters_after_a_failed_call(pkg, engines, stream):
+    """a one-launch call whose recipients' decodes fail in chunk 1, then an honest one-launch call directly after it on the same
+    engines and stream: the first counts what the model fails, the second reports nothing in either summary -- the last workgroup of
+    the first left the counter pair [24] (and [0], which no input can drive: the revealed values' decode reads what the kernel wrote)
+    at zero.  Two chunks at n = 5, t = 1; both_forms_match asserts that the kernel ran"""
+    n, t, G = 5, 1, 2
+    M = t + 1
+    contrib, _, hb_q, lk, hm = honest(n, t, G)
+    b_q = hb_q.copy()
+    b_q[0, M + 1] = (int(b_q[0, M + 1]) + 5) % P
+    m = model(n, t, contrib, b_q, lk)
+    assert m["summary_first"] == (n, n, 1, DECODING_ERROR) and m["summary"] == NO_FAILURE
+    assert hm["summary_first"] == NO_FAILURE and hm["summary"] == NO_FAILURE
+    both_forms_match(engines, pkg, stream, n, t, contrib, b_q, m, forms=(FORCED,))
+    both_forms_match(engines, pkg, stream, n, t, contrib, hb_q, hm, forms=(FORCED,))
+
+
 def test_sat32_context_takes_the_separate_launches(pkg, engines, stream):
     """a Sat32 Fr context never takes the kernel: with the threshold forced up it gives the bytes of U29"""
     n, t = 7, 2

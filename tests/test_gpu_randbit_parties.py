@@ -305,6 +305,33 @@ def test_tampered_shares(pkg, stream, field, n, t):
         eng.close()
 
 
+@pytest.mark.parametrize("field", ["goldilocks", "fr"])
+def test_counters_after_a_failed_call(pkg, stream, field):
+    """a one-launch call whose two opens fail (the recipients' decodes of d-chunk 0 and of the squares' chunk 1), then an honest
+    one-launch call directly after it on the same engine and stream: the first counts what the model fails, the second reports
+    nothing in any of the four summaries -- the last workgroup of the first left the counter pairs [24], [26] (and [0], [28], which
+    no input can drive: the revealed values' decodes read what the kernel wrote) at zero.  Two chunks at n = 4, t = 1"""
+    n, t, G = 4, 1, 2
+    M = t + 1
+    N = G * M
+
+    def both_opens(bad, sec):
+        bad["ta"][1, 0] = bad["ta"][0, 0]
+        bad["tc"][2, M] = bad["tc"][1, M]
+
+    sh = tampered(field, n, t, N, both_opens)
+    m = model(field, n, t, sh)
+    assert m["sm_de_first"] == (n, n, 0, DECODING_ERROR) and m["sm_sq_first"] == (n, n, 1, DECODING_ERROR)
+    _, hsh, hm = honest(field, n, t, N)
+    assert all(hm[k] == (0, 0, 0xFFFFFFFF, 0) for k in ("sm_de_first", "sm_de", "sm_sq_first", "sm_sq"))
+    eng = engine(pkg, field)
+    try:
+        both_forms_match(eng, stream, field, n, t, sh, m, forms=(FORCED,))
+        both_forms_match(eng, stream, field, n, t, hsh, hm, forms=(FORCED,))
+    finally:
+        eng.close()
+
+
 def _no_root_delta(field, a):
     """delta with a^2 + delta a non-residue (ark's sqrt has no root)"""
     q = RB.PRIME[field]

@@ -86,12 +86,12 @@ def collect(eng, tp, with_w, stream=0):
     return got
 
 
-def run_forms(pkg, eng, n, t, N, k, m, ins, open_senders=None, stream=0, check=False, graph=False):
+def run_forms(pkg, eng, n, t, N, k, m, ins, open_senders=None, stream=0, check=False, graph=False, forms=FORMS):
     """the same inputs through both forms; returns {form: buffers}.  The default threshold is put back."""
     H = pkg.hbmpc
     res = {}
     try:
-        for form, fused in FORMS:
+        for form, fused in forms:
             eng.set_fused_truncpr(fused)
             tp = make_pipe(pkg, eng, n, t, N, k, m, ins, stream=stream, open_senders=open_senders)
             try:

@@ -16,7 +16,7 @@ from oracle import cref as O
 from tests import edge_inputs as X
 from tests import test_gpu_mul as M
 from tests import test_gpu_truncpr as T
-from tests.sender_sets import fpmul_expected, summary_tail
+from tests.sender_sets import fpmul_expected, fpmul_inputs, summary_tail
 from tests.test_gpu_mul import pkg_eng, pkg_gl  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -36,8 +36,9 @@ def arrays(F, case, n):
 
 
 # ---- Mul -------------------------------------------------------------------------------------------------------------------------
-def run_mul(pkg, eng, F, n, t, N, ins, ids, forms=M.FORMS):
-    """hbmpc_[gl_]dev_mul_parties with these sender ids under each threshold setting; {form: buffers}"""
+def run_mul(pkg, eng, F, n, t, N, ins, ids, forms=M.FORMS, desh_marker=None):
+    """hbmpc_[gl_]dev_mul_parties with these sender ids under each threshold setting; {form: buffers}.  desh_marker: what the
+    separate launches' workspace holds before each call (the one launch leaves it alone), returned as "desh" """
     mp = pkg.pipelines.Mul(eng, n, t, N)
     got = {}
     try:
@@ -46,8 +47,12 @@ def run_mul(pkg, eng, F, n, t, N, ins, ids, forms=M.FORMS):
             eng.set_fused_mul(fused)
             eng.h2d(mp.out, F.arr([[0] * N] * n))
             eng.h2d(mp.deop, F.arr([0] * (2 * N)))
+            if desh_marker is not None:
+                mp.upload_named("desh", desh_marker)
             assert M.raw_call(eng, mp, ids, n, t, N) == 0
             got[form] = M.collect(eng, mp)
+            if desh_marker is not None:
+                got[form]["desh"] = mp.download("desh").copy()
     finally:
         eng.set_fused_mul(pkg.hbmpc.FUSED_MUL_DEFAULT)
         mp.close()
@@ -159,12 +164,12 @@ FPMUL_FORMS = {"one": (1 << 20, NEVER), "four": (0, 0), "five": (0, NEVER)}     
 FPMUL_NAMES = ("dop", "eop", "z", "rdash", "osh", "cop", "out")
 
 
-def run_fpmul(pkg, eng, n, t, N, k, m, ins, forms_known=True):
+def run_fpmul(pkg, eng, n, t, N, k, m, ins, forms_known=True, forms=tuple(FPMUL_FORMS)):
     """the three forms, set as tests/test_gpu_pipelines.py::test_fpmul_one_launch_equals_five sets them; defaults restored"""
     res = {}
     marker = O.fill_random(77, 2 * n * N).reshape(n, 2, N, 4)
     try:
-        for form, (fused, pair_min) in FPMUL_FORMS.items():
+        for form, (fused, pair_min) in ((f, FPMUL_FORMS[f]) for f in forms):
             assert eng.L.hbmpc_set_fused_fpmul(eng.ctx, C.c_size_t(fused)) == 0
             assert eng.L.hbmpc_set_fpmul_pair_decode(eng.ctx, C.c_size_t(pair_min)) == 0
             eng.set_matrix_cores(True, 32 if form == "four" else 65536)
@@ -191,9 +196,9 @@ def run_fpmul(pkg, eng, n, t, N, k, m, ins, forms_known=True):
     return res
 
 
-def check_fpmul(pkg, eng, n, t, N, k, m, ins, tag, forms_known=True):
+def check_fpmul(pkg, eng, n, t, N, k, m, ins, tag, forms_known=True, forms=tuple(FPMUL_FORMS)):
     want = fpmul_expected(ins, n, t, N, k, m)
-    res = run_fpmul(pkg, eng, n, t, N, k, m, ins, forms_known)
+    res = run_fpmul(pkg, eng, n, t, N, k, m, ins, forms_known, forms)
     for form, got in res.items():
         for nm in FPMUL_NAMES + ("status",):
             assert np.array_equal(got[nm], want[nm]), (tag, form, nm)
@@ -234,22 +239,25 @@ def triple_expected(F, ins, n, t, N):
     Y = np.stack([F.O.vandermonde_apply(loc[p].reshape((G, m) + F.tail), n, 2 * t)[1] for p in range(n)])      # [party][recipient][chunk]
     Z, st1 = [], []
     for j in range(n):
-        rc, z, st = F.O.batch_recover_p0(ids, np.ascontiguousarray(Y[:, j]), n, 2 * t, t)
-        assert rc == 0
+        rc, z, st = F.O.batch_recover_p0(ids, np.ascontiguousarray(Y[:, j]), n, 2 * t, t)    # a failed chunk: zero, status = its error
+        assert rc == (8 if st.any() else 0)
         Z.append(z), st1.append(st)
     Z = np.stack(Z)
     rc, opened, nco, st2 = F.O.batch_recover(ids, Z, n, 2 * t, t)
     assert rc == 0
     opened = np.ascontiguousarray(opened).reshape((N,) + F.tail)
     c = np.stack([F.O.triple_finalize(ins["rt"][p], opened)[1] for p in range(n)])
-    return {"c": c, "Y": Y, "Z": Z, "opened": opened, "status": np.concatenate([st2] + st1[1:])}
+    return {"c": c, "Y": Y, "Z": Z, "opened": opened, "status": np.concatenate([st2] + st1[1:]), "status_first": np.concatenate(st1)}
 
 
-def run_triplegen(pkg, eng, n, t, N, ins):
+TRIPLE_FORMS = (("one", 1 << 20), ("four", 0))
+
+
+def run_triplegen(pkg, eng, n, t, N, ins, forms=TRIPLE_FORMS):
     G = N // (2 * t + 1)
     res = {}
     try:
-        for form, fused in (("one", 1 << 20), ("four", 0)):
+        for form, fused in forms:
             assert eng.L.hbmpc_set_fused_triplegen(eng.ctx, C.c_size_t(fused)) == 0
             tg = pkg.pipelines.TripleGen(eng, n, t, N)
             try:
@@ -340,3 +348,87 @@ def test_fpmul_single_bit_tampering(pkg_eng, n, t):
     assert [int(i) for i in np.flatnonzero(want["status"][:N])] == case["failing_second"]
     assert [N + int(i) for i in np.flatnonzero(want["status"][N:])] == [c for c in case["failing_first"] if c >= N]
     assert not want["cop"][case["failing_second"]].any() and not np.concatenate([want["dop"], want["eop"]])[case["failing_first"]].any()
+
+
+# ---- the decode counters behind the summaries ------------------------------------------------------------------------------------------
+# A one-launch call whose opens fail, then an honest one-launch call on the same stream with nothing in between: the first must
+# count exactly what the oracle fails, the second must report nothing -- the last workgroup of the first left every counter it
+# used at zero.  n = 4, t = 1 and 5 elements: two workgroups (fewer than the 16 sub-tickets), the second with one live wave;
+# two chunks for the workgroup kernel.  One bit of one sender's share is flipped per failing chunk.
+def flip_bit(arr, party, el):
+    arr[(party, el) + (0,) * (arr.ndim - 2)] ^= np.uint64(1)
+
+
+def test_mul_counters_after_a_failed_call(pkg_eng):
+    pkg, eng = pkg_eng
+    n, t, N, ids = 4, 1, 5, (0, 1, 2)
+    honest = M.inputs(M.FR, n, t, N, 9100)
+    bad = M.tampered(honest)
+    flip_bit(bad["ta"], 1, 4)                                                            # a - x of element 4: chunk 4
+    flip_bit(bad["tb"], 2, 0)                                                            # b - y of element 0: chunk N
+    marker = O.fill_random(78, 2 * n * N).reshape(n, 2, N, 4)
+    for ins, failing in ((bad, [4, N]), (honest, [])):
+        want = M.expected(M.FR, ins, n, t, N, ids)
+        assert [int(i) for i in np.flatnonzero(want["status"])] == failing
+        got = run_mul(pkg, eng, X.FR, n, t, N, ins, ids, forms=M.FORMS[:1], desh_marker=marker)["one"]
+        assert np.array_equal(got["desh"], marker), "the separate launches ran"           # their workspace: the one launch leaves it alone
+        M.assert_equals_oracle(got, want, failing)
+        assert got["summary"].tolist()[1:] == summary_tail(want["status"]) == ([2, 4, 8] if failing else NOTHING_FAILED[1:])
+    assert got["summary"].tolist() == NOTHING_FAILED
+    multi = run_mul(pkg, eng, X.FR, n, t, N, honest, ids, forms=M.FORMS[1:], desh_marker=marker)["multi"]
+    assert not np.array_equal(multi["desh"], marker)                                     # (the marker does tell the forms apart)
+
+
+@pytest.mark.parametrize("with_w", [False, True], ids=["truncpr", "fpdivconst"])
+def test_truncpr_counters_after_a_failed_call(pkg_eng, with_w):
+    """(the call has no workspace and every buffer holds the same bytes in both forms, so nothing a caller can see tells which form
+    ran: that this shape under this threshold takes the one launch is pinned by tests/test_protocol_routes.py on the planner itself)"""
+    pkg, eng = pkg_eng
+    n, t, N, k, m = 4, 1, 5, 32, 4
+    honest = T.random_inputs(n, t, N, m, 9200, with_w)
+    bad = dict(honest, a=honest["a"].copy())
+    flip_bit(bad["a"], 1, 4)
+    for ins, failing in ((bad, [4]), (honest, [])):
+        want = T.expected(ins, n, t, N, k, m, 2 * t + 1)
+        assert [int(i) for i in np.flatnonzero(want["status"])] == failing
+        got = T.run_forms(pkg, eng, n, t, N, k, m, ins, forms=T.FORMS[:1])["one"]
+        T.assert_equals_oracle(got, want, with_w, failing)
+        assert got["summary"].tolist()[1:] == summary_tail(want["status"]) == ([1, 4, 8] if failing else NOTHING_FAILED[1:])
+    assert got["summary"].tolist() == NOTHING_FAILED
+
+
+def test_fpmul_counters_after_a_failed_call(pkg_eng):
+    """both pairs of counters: the first open's ([24], [25]) and the second's ([0], [1])"""
+    pkg, eng = pkg_eng
+    n, t, N, k, m = 4, 1, 5, 32, 4
+    honest = fpmul_inputs(n, t, N, m)
+    bad = {nm: v.copy() for nm, v in honest.items()}
+    flip_bit(bad["ta"], 1, 4)                                                            # the first open, chunk 4
+    flip_bit(bad["rint"], 2, 2)                                                          # the second open, chunk 2
+    for ins, first, second in ((bad, [1, 4, 8], [1, 2, 8]), (honest, NOTHING_FAILED[1:], NOTHING_FAILED[1:])):
+        want = check_fpmul(pkg, eng, n, t, N, k, m, ins, ("counters", first), forms=("one",))   # (asserts that the one launch ran)
+        assert want["summary_first"] == first and want["summary"] == second
+
+
+@pytest.mark.parametrize("field", ["fr", "goldilocks"])
+def test_triplegen_counters_after_a_failed_call(pkg_eng, pkg_gl, field):
+    """the recipients' decodes ([24], [25]).  The revealed values' decode ([0], [1]) reads what the kernel itself wrote -- every
+    party is a sender of every recipient's decode, so a tampered chunk reveals n zeros, which lie on the zero polynomial: no input
+    makes it fail.  (Y, Z and c hold the same bytes in both forms -- c is the four launches' workspace before it is their output -- so
+    which form ran is pinned by tests/test_protocol_routes.py on the planner, not here)"""
+    (pkg, eng), F = (pkg_eng, M.FR) if field == "fr" else (pkg_gl, M.GL)
+    n, t, G = 4, 1, 2
+    N = G * (2 * t + 1)
+    r = F.O.fill_random(9402, N)
+    honest = {"a": F.share_all(F.O.fill_random(9400, N), n, t, 9410), "b": F.share_all(F.O.fill_random(9401, N), n, t, 9411),
+              "r2t": F.share_all(r, n, 2 * t, 9412), "rt": F.share_all(r, n, t, 9413)}
+    bad = {nm: v.copy() for nm, v in honest.items()}
+    flip_bit(bad["a"], 1, 4)                                                             # chunk 1, for every recipient
+    for ins, first in ((bad, [n, 1, 8]), (honest, NOTHING_FAILED[1:])):
+        want = triple_expected(F, ins, n, t, N)
+        assert summary_tail(want["status_first"]) == first and not want["status"][:G].any()
+        got = run_triplegen(pkg, eng, n, t, N, ins, forms=TRIPLE_FORMS[:1])["one"]
+        for nm in ("c", "Y", "Z", "opened", "status"):
+            assert np.array_equal(got[nm], want[nm]), (first, nm)
+        assert got["summary_first"].tolist()[1:] == first and got["summary"].tolist() == NOTHING_FAILED
+    assert got["summary_first"].tolist() == NOTHING_FAILED
