@@ -201,6 +201,8 @@ void hbmpc_graph_destroy(hbmpc_graph* graph);
  *   fpmul          x, y, ta, tb, tc, rint ([n][N]), rbits ([n][m][N]) (inputs); out ([n][N]); z, rdash, osh, desh, dop, eop, cop
  *   truncpr        a, rint, rbits (inputs; w with a multiplier); out; c, rdash, osh, cop, status, summary (see its create call)
  *   mul            x, y, ta, tb, tc (inputs [n][N]); out ([n][N] = z); desh ([n][2][N]); deop ([2 N]; dop, eop its halves); status (2 N bytes); summary
+ *   input          x ([N]), r ([n][N]) (inputs); mask, masked ([N]); out ([n][N]); status (N bytes); summary
+ *   output         sh (input [n][N]); out ([N]); status (N bytes); summary
  *   ransha         coeffs ([dealer][K][t+1], column 0 the secret); S ([dealer][recipient][K]); y; out ([party][K][n-2t]); bad
  *   randousha      coeffs_t, coeffs_2t; S_t, S_2t; y_t, y_2t; out_t, out_2t ([party][K][t+1]); bad
  *   preprocessing  its parts by name (hbmpc_pipe_part: "ransha", "randousha", "triplegen"; borrowed handles)
@@ -226,6 +228,15 @@ ShareErrorCode hbmpc_pipe_truncpr_create(hbmpc_ctx* ctx, size_t n, size_t t, siz
  * hbmpc_gl_dev_mul_parties.  Buffers: x, y, ta, tb, tc (inputs [n][N]); out ([n][N]); desh ([n][2][N]); deop ([2 N]: the opened
  * ta - x, then the opened tb - y; dop and eop name its halves); status (2 N bytes); summary.  open_senders as in fpmul. */
 ShareErrorCode hbmpc_pipe_mul_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t open_senders, void* stream, hbmpc_pipe** pipe_out);
+/* Input (honeybadger/input/input.rs:489-506, 85-100, 300-301) of N client values for n parties, over either field: out = the parties'
+ * shares of x from one random mask per value, whose shares r the caller uploads (RanSha's outputs).  run() is hbmpc_dev_input_parties /
+ * hbmpc_gl_dev_input_parties with parties 0 .. open_senders - 1 as the senders (0: 2t + 1); checked, it returns DecodingError where the
+ * reference's `?` would.  Buffers: x ([N]), r ([n][N]) (inputs); mask, masked ([N]); out ([n][N]); status (N bytes); summary. */
+ShareErrorCode hbmpc_pipe_input_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t open_senders, void* stream, hbmpc_pipe** pipe_out);
+/* Output (honeybadger/output/output.rs:157-177) of N result values from n parties' shares, over either field: run() is
+ * hbmpc_dev_output_parties / hbmpc_gl_dev_output_parties, senders and checking as in input.  Buffers: sh (input [n][N]); out ([N]);
+ * status (N bytes); summary. */
+ShareErrorCode hbmpc_pipe_output_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t open_senders, void* stream, hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_ransha_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t K, size_t verify_senders, void* stream,
                                         hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_randousha_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t K, void* stream, hbmpc_pipe** pipe_out);
@@ -618,6 +629,40 @@ ShareErrorCode hbmpc_gl_dev_mul_parties(hbmpc_ctx* ctx, const size_t* sender_ids
                                         const uint64_t* c, const uint64_t* x, const uint64_t* y, size_t N, size_t n, size_t t,
                                         uint64_t* de_sh_ws, uint64_t* de_out, uint64_t* z_out, uint8_t* status_out,
                                         hbmpc_recover_summary* summary_dev, void* stream);
+/* Input for every party of this device in one call (honeybadger/input/input.rs): the client's open of one mask per value
+ * (:489-502: recover_secret(.., n, t) per element from the servers' shares), the masked values it broadcasts (:503-506) and the
+ * share every server keeps (:85-100, :300-301):
+ *   mask_out   = the P(0) decode of degree t of the senders' rows of r_sh
+ *   masked_out = x + mask
+ *   in_sh_out  = masked - r_sh, for every party
+ * x, mask_out and masked_out are [N]; r_sh and in_sh_out are [party][N]; sender_ids[S] are PARTY ids, as in hbmpc_dev_mul_parties.
+ * mask_out, status_out[N] (REQUIRED) and summary_dev (may be null) hold exactly what hbmpc_dev_batch_recover_p0 leaves for G = N,
+ * d = t from the senders' rows.  Element g is opened iff status_out[g] < 2 (0 optimistic, 1 fallback).  An element that is not
+ * opened is REFUSED: mask_out[g], masked_out[g] and in_sh_out[p][g] of every party are zero -- never x[g] + 0, which would
+ * broadcast the client's value in the clear (the reference returns the error and broadcasts nothing, :499-502).  The call still
+ * returns ShareSuccess and counts the element in the summary, like its siblings.  All validation (null buffers, N == 0, n == 0,
+ * n > 255, the senders) happens before the first launch: a call that is refused has written nothing.
+ * With exactly 2t + 1 senders and at most hbmpc_set_fused_input elements the Fr call is ONE launch, a wave per element
+ * (csrc/kernels_input_wave.hpp: U29, n <= 64, t <= 30); otherwise two: the P(0) decode with every sender's row read in place
+ * (hbmpc_dev_batch_recover_slots; robust, with the OEC / Gao fallback when S > 2t + 1) and one element-wise launch for all
+ * parties.  The Goldilocks call is always the two launches.  Every output buffer, status byte and summary holds the same bytes in
+ * either form.  TypeMismatch: the Fr call on a Goldilocks context and the other way round.
+ * Not here: sessions, RBC, the InputMessage / OutputMessage envelopes, the 48-byte payloads (hbmpc_dev_unpack_shares /
+ * hbmpc_dev_pack_fvec), sampling the masks (RanSha's outputs). */
+ShareErrorCode hbmpc_dev_input_parties(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const U256* x, const U256* r_sh, size_t N, size_t n,
+                                       size_t t, U256* mask_out, U256* masked_out, U256* in_sh_out, uint8_t* status_out,
+                                       hbmpc_recover_summary* summary_dev, void* stream);
+ShareErrorCode hbmpc_gl_dev_input_parties(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const uint64_t* x, const uint64_t* r_sh, size_t N,
+                                          size_t n, size_t t, uint64_t* mask_out, uint64_t* masked_out, uint64_t* in_sh_out, uint8_t* status_out,
+                                          hbmpc_recover_summary* summary_dev, void* stream);
+/* Output's client side for a device that holds every party's result shares (honeybadger/output/output.rs:157-177):
+ * recover_secret(.., n, t) per element.  sh is [party][N], sender_ids[S] PARTY ids, out [N]; out, status_out[N] and summary_dev (either
+ * may be null) hold exactly what hbmpc_dev_batch_recover_p0 leaves for G = N, d = t from the senders' rows, which are read in place
+ * (one launch at exactly 2t + 1 senders).  An element with status >= 2 is one at which the reference returns its error. */
+ShareErrorCode hbmpc_dev_output_parties(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const U256* sh, size_t N, size_t n, size_t t, U256* out,
+                                        uint8_t* status_out, hbmpc_recover_summary* summary_dev, void* stream);
+ShareErrorCode hbmpc_gl_dev_output_parties(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const uint64_t* sh, size_t N, size_t n, size_t t,
+                                           uint64_t* out, uint8_t* status_out, hbmpc_recover_summary* summary_dev, void* stream);
 /* TruncPrNode on its own for every party of this device (fpmul/truncpr.rs:185-318), and with w_dev FPDivConstNode
  * (fpdiv/fpdiv_const.rs:61-99; div_with_const_fixed, honeybadger/mod.rs:1071-1137): a local product with a PUBLIC multiplier per
  * element, then the same TruncPr.  With v = a * w[i] when w_dev is given and v = a otherwise:
@@ -1077,6 +1122,9 @@ ShareErrorCode hbmpc_set_fused_truncpr(hbmpc_ctx* ctx, size_t max_elements);
 /* hbmpc_dev_mul_parties runs as one launch up to max_elements batch elements (default 1024; 0: always the three separate
  * launches).  Same bytes either way (A/B aid). */
 ShareErrorCode hbmpc_set_fused_mul(hbmpc_ctx* ctx, size_t max_elements);
+/* hbmpc_dev_input_parties runs as one launch up to max_elements batch elements (default 768; 0: always the two separate
+ * launches).  Same bytes either way (A/B aid). */
+ShareErrorCode hbmpc_set_fused_input(hbmpc_ctx* ctx, size_t max_elements);
 /* hbmpc_[gl_]dev_randbit_parties runs as one launch up to max_chunks chunks of t + 1 elements (default 256 over Fr, 1024 over
  * Goldilocks; 0: always the nine separate launches).  Same bytes either way (A/B aid). */
 ShareErrorCode hbmpc_set_fused_randbit(hbmpc_ctx* ctx, size_t max_chunks);

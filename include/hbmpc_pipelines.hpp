@@ -10,6 +10,9 @@
 //                  fpmul/fpmul.rs:61-110, mul/multiplication.rs:417-426,57-139, fpmul/truncpr.rs:185-318
 //   Mul            Multiply (Beaver, RBC path): the opened shares, the open, finalize_mul
 //                  honeybadger/mod.rs:543-628, mul/multiplication.rs:417-426,102-139,57-100
+//   Input          the client's open of the masks, masked = x + mask, the servers' masked - r
+//                  honeybadger/input/input.rs:489-506, 85-100, 300-301
+//   Output         the client's open of the result shares                           honeybadger/output/output.rs:157-177
 //   TruncPr        TruncPrNode on its own                                           fpmul/truncpr.rs:185-318
 //   FpDivConst     FPDivConstNode: a * w for a public reciprocal w, then TruncPr    fpdiv/fpdiv_const.rs:61-99, fpdiv/mod.rs:8-60
 //   RanSha         RanShaNode: deal, n x n Vandermonde, verifier reconstruction + degree test, output slice
@@ -135,6 +138,45 @@ class Mul : public Pipeline {
     static hbmpc_pipe* create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t open_senders, void* stream) {
         hbmpc_pipe* h = nullptr;
         pl_check(hbmpc_pipe_mul_create(ctx, n, t, N, open_senders, stream, &h), ctx, "hbmpc_pipe_mul_create");
+        return h;
+    }
+};
+
+// Input (honeybadger/input/input.rs:489-506, 85-100, 300-301) of N client values for n parties over Fr: out = the parties' shares of
+// x from one random mask per value, whose shares r the caller uploads.  An element whose mask does not open is refused (zeros in
+// mask, masked and out); a checked run() then throws.  open_senders as in FpMul.  (A Goldilocks context takes the same handle through
+// the C ABI; this class names its buffers as U256.)
+class Input : public Pipeline {
+  public:
+    Input(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream, size_t open_senders = 0)
+        : Pipeline(ctx, create(ctx, n, t, N, open_senders, stream), stream) {
+        x = buffer("x"), r = buffer("r"), mask = buffer("mask"), masked = buffer("masked"), out = buffer("out");
+    }
+    U256 *x, *mask, *masked;  // [N]
+    U256 *r, *out;            // [party][N]
+
+  private:
+    static hbmpc_pipe* create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t open_senders, void* stream) {
+        hbmpc_pipe* h = nullptr;
+        pl_check(hbmpc_pipe_input_create(ctx, n, t, N, open_senders, stream, &h), ctx, "hbmpc_pipe_input_create");
+        return h;
+    }
+};
+
+// Output (honeybadger/output/output.rs:157-177) of N result values from the n parties' shares sh over Fr: out = what they open to.
+class Output : public Pipeline {
+  public:
+    Output(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, void* stream, size_t open_senders = 0)
+        : Pipeline(ctx, create(ctx, n, t, N, open_senders, stream), stream) {
+        sh = buffer("sh"), out = buffer("out");
+    }
+    U256* sh;   // [party][N]
+    U256* out;  // [N]
+
+  private:
+    static hbmpc_pipe* create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t open_senders, void* stream) {
+        hbmpc_pipe* h = nullptr;
+        pl_check(hbmpc_pipe_output_create(ctx, n, t, N, open_senders, stream, &h), ctx, "hbmpc_pipe_output_create");
         return h;
     }
 };

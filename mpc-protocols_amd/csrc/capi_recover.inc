@@ -145,7 +145,7 @@ RecoverKnobs recover_knobs(const hbmpc_ctx* ctx) {
 // ... and of the protocol calls' rule (protocol_route.hpp)
 ProtocolKnobs protocol_knobs(const hbmpc_ctx* ctx) {
     return ProtocolKnobs{ctx->impl, ctx->force_generic, ctx->direct_fail, ctx->fused_triplegen_max, ctx->fused_fpmul_max, ctx->fused_truncpr_max,
-                         ctx->fused_mul_max, ctx->fused_randbit_max, ctx->pair_decode_min};
+                         ctx->fused_mul_max, ctx->fused_randbit_max, ctx->pair_decode_min, ctx->fused_input_max};
 }
 
 // One batch decode.  Its forms (group, second_coeff, only_coeff, pair) are those of RecoverShape (recover_route.hpp); a form that

@@ -21,6 +21,7 @@
 #include "kernels_fpmul_wave.hpp"
 #include "kernels_truncpr_wave.hpp"
 #include "kernels_mul_wave.hpp"
+#include "kernels_input_wave.hpp"
 #include "kernels_triplegen_wg.hpp"
 #include "kernels_randbit_wg.hpp"
 #include "kernels_prandbit_wg.hpp"
@@ -87,6 +88,7 @@ struct hbmpc_ctx {
     size_t fused_fpmul_max = 2048;                 // hbmpc_dev_fpmul_parties: one launch (a wave per element) up to this many elements (0: never)
     size_t fused_truncpr_max = 768;                // hbmpc_dev_truncpr_parties: the same (profiles/fused_truncpr_sweep.txt: ahead or level, eager and replayed)
     size_t fused_mul_max = 1024;                   // hbmpc_dev_mul_parties: the same (profiles/fused_mul_sweep.txt: ahead both eager and replayed)
+    size_t fused_input_max = 768;                  // hbmpc_dev_input_parties: the same (profiles/fused_input_sweep.txt)
     size_t fused_randbit_max = FUSED_RANDBIT_FR;   // hbmpc_dev_randbit_parties: one launch (a workgroup per chunk of t + 1 elements) up to this many chunks (0: never); per field, hbmpc_create
     size_t fused_prandbit_max = FUSED_PRANDBIT;    // hbmpc_dev_prandbit_parties / _prandint_parties (read from the Fr context): the same, in chunks of t + 1 elements
     bool gather_row_copies = false;                // hbmpc_dev_gather_party_major: take the per-row peer copies even where the 2-D copy applies (A/B aid)
@@ -457,6 +459,7 @@ KNOB_SETTER(hbmpc_set_fused_fpmul, fused_fpmul_max)
 KNOB_SETTER(hbmpc_set_fused_truncpr, fused_truncpr_max)
 KNOB_SETTER(hbmpc_set_fused_triplegen, fused_triplegen_max)
 KNOB_SETTER(hbmpc_set_fused_mul, fused_mul_max)
+KNOB_SETTER(hbmpc_set_fused_input, fused_input_max)
 KNOB_SETTER(hbmpc_set_fused_randbit, fused_randbit_max)
 KNOB_SETTER(hbmpc_set_fused_prandbit, fused_prandbit_max)
 KNOB_SETTER(hbmpc_set_fpmul_pair_decode, pair_decode_min)
@@ -2291,5 +2294,6 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
 
 #include "capi_truncpr.inc"
 #include "capi_mul.inc"
+#include "capi_input.inc"
 #include "capi_randbit.inc"
 #include "capi_prandbit.inc"

@@ -353,6 +353,48 @@ __global__ __launch_bounds__(256) void k_truncpr_finalize(const uint32_t* __rest
     F::store_lt2r(out + ip * F::EW, F::mulc(t, cs.c0));
 }
 
+// Input's last step after the masks are opened (input/input.rs:503-506, 85-100, 300-301), for every party in ONE launch:
+//   masked = x + mask;   in_sh[p] = masked - r[p]
+// x, mask, status are [N]; r, in_sh [party][N].  gridDim.y = parties + 1: row p < parties writes party p's shares, the row after the
+// last writes the public values.  An element whose mask did not open (status >= 2: neither optimistic nor fallback) is REFUSED:
+// its mask, its masked value and every share are zero -- never x + 0, the client's input in the clear.
+template <class F>
+__global__ __launch_bounds__(256) void k_input_finish(const uint8_t* __restrict__ status, uint32_t* __restrict__ mask,
+                                                      const uint32_t* __restrict__ x, const uint32_t* __restrict__ r, size_t N,
+                                                      uint32_t* __restrict__ masked, uint32_t* __restrict__ in_sh) {
+    HB_GID
+    const size_t row = lin_ % gridDim.y;
+    const bool pub = row == gridDim.y - 1, ok = status[i] < 2;
+    const size_t ip = row * N + i;
+    if constexpr (F::EW == 8) {
+        uint32_t a8[8], b8[8], m8[8], o8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (!ok) {
+            if (pub) raw_store8(mask + i * 8, o8), raw_store8(masked + i * 8, o8);
+            else raw_store8(in_sh + ip * 8, o8);
+            return;
+        }
+        raw_load8(x + i * 8, a8), raw_load8(mask + i * 8, b8);
+        raw_add_mod(a8, b8, m8);
+        if (pub) {
+            raw_store8(masked + i * 8, m8);
+        } else {
+            raw_load8(r + ip * 8, b8);
+            raw_sub_mod(m8, b8, o8);
+            raw_store8(in_sh + ip * 8, o8);
+        }
+    } else {
+        using E = typename F::E;
+        if (!ok) {
+            if (pub) F::store_loose(mask + i * F::EW, F::zero()), F::store_loose(masked + i * F::EW, F::zero());
+            else F::store_loose(in_sh + ip * F::EW, F::zero());
+            return;
+        }
+        const E m = F::add(F::load(x + i * F::EW), F::load(mask + i * F::EW));
+        if (pub) F::store_loose(masked + i * F::EW, m);
+        else F::store_loose(in_sh + ip * F::EW, F::template sub<2>(m, F::load(r + ip * F::EW)));
+    }
+}
+
 // register-resident Montgomery-multiply chain: the integer-ALU ceiling of the field implementation
 template <class F>
 __global__ __launch_bounds__(256) void k_modmul_ubench(uint32_t* __restrict__ out, uint32_t iters, ElemConsts cs) {

@@ -127,6 +127,9 @@ bool launch_truncpr_wave(const TruncprWaveArgs& a, int device, hipStream_t s, bo
 // Multiply (Beaver) the same way (kernels_mul_wave.hpp)
 struct MulWaveArgs;
 bool launch_mul_wave(const MulWaveArgs& a, int device, hipStream_t s, bool dry_run);
+// Input the same way (kernels_input_wave.hpp)
+struct InputWaveArgs;
+bool launch_input_wave(const InputWaveArgs& a, int device, hipStream_t s, bool dry_run);
 // flagged chunks: two cheap interpolation candidates before the OEC/Gao kernel (k_second_chance)
 void launch_second_chance(int impl, const SecondArgs& a, unsigned grid, hipStream_t s);
 bool launch_second_chance_m(int m, const SecondArgs& a, unsigned grid, hipStream_t s);  // U29, m = 2 .. 16 at compile time; false otherwise
@@ -196,6 +199,9 @@ void launch_truncpr_front(int impl, const uint32_t* a, const uint32_t* w, const 
                           unsigned grid_parties, hipStream_t s);  // w null: no multiplier (c is not written)
 void launch_truncpr_finalize(int impl, const uint32_t* a, const uint32_t* r_dash, const uint32_t* c_open, int m, size_t N, unsigned parties,
                              const ElemConsts& cs, uint32_t* d_out, hipStream_t s);
+// Input after the open, either field: masked = x + mask, in_sh[p] = masked - r[p]; a mask that did not open (status >= 2) leaves zeros
+void launch_input_finish(int impl, const uint8_t* status, uint32_t* mask, const uint32_t* x, const uint32_t* r, size_t N, unsigned parties, uint32_t* masked,
+                         uint32_t* in_sh, hipStream_t s);
 void launch_modmul_ubench(int impl, uint32_t* out, size_t threads, uint32_t iters, const ElemConsts& cs, hipStream_t s);
 void launch_traffic_ubench(unsigned wgs, const uint4* x, size_t G, int m, uint4* y, int n, hipStream_t s);
 // square roots, inverses, RandBit's last step (tu_sqrt.hip, kernels_sqrt.hpp)

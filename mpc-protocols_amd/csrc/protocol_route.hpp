@@ -1,7 +1,8 @@
 // protocol_route.hpp -- which form a "whole protocol step for all parties" call takes: ONE place for the rule (plain C++, no HIP).
 //
-// hbmpc_[gl_]dev_triplegen_parties, hbmpc_dev_fpmul_parties, hbmpc_dev_truncpr_parties, hbmpc_[gl_]dev_mul_parties and
-// hbmpc_[gl_]dev_randbit_parties each ask plan_protocol once; either form writes the same bytes to every output buffer.
+// hbmpc_[gl_]dev_triplegen_parties, hbmpc_dev_fpmul_parties, hbmpc_dev_truncpr_parties, hbmpc_[gl_]dev_mul_parties,
+// hbmpc_[gl_]dev_randbit_parties and hbmpc_[gl_]dev_input_parties each ask plan_protocol once; either form writes the same bytes
+// to every output buffer.
 // Two declines stay with the executor because they depend on a launcher or on the decode, not on the call's shape:
 //   - the launchers' dry run (launch_*_wave(.., true): the LDS size and the LDS attribute): the call then runs its separate launches;
 //   - the HBMPC_NOT_FUSED answer of batch_recover_dev to the pair form: the open then writes the shares and decodes them.
@@ -18,18 +19,19 @@ struct ProtocolKnobs {
     bool force_generic, direct_fail;
     size_t fused_triplegen_max, fused_fpmul_max, fused_truncpr_max, fused_mul_max, fused_randbit_max;  // chunks, 3 x elements, chunks
     size_t pair_decode_min;
+    size_t fused_input_max = 0;  // elements; last, with a default: callers that list the fields above stay as they are
 };
-enum class ProtocolCall { TripleGen, FpMul, TruncPr, Mul, RandBit };
-// the call: N elements per party, n parties, t faults, S senders (FPMul, TruncPr, Mul), m truncated bits (FPMul)
+enum class ProtocolCall { TripleGen, FpMul, TruncPr, Mul, RandBit, Input };
+// the call: N elements per party, n parties, t faults, S senders (FPMul, TruncPr, Mul, Input), m truncated bits (FPMul)
 struct ProtocolShape {
     ProtocolCall call;
     size_t N, n, t, S, m;
 };
 struct ProtocolPlan {
-    bool one_launch;  // a wave per element (FPMul, TruncPr, Mul) or a workgroup per chunk (TripleGen, RandBit) instead of the separate launches
+    bool one_launch;  // a wave per element (FPMul, TruncPr, Mul, Input) or a workgroup per chunk (TripleGen, RandBit) instead of the separate launches
     // the wave kernels: 1 << lk adjacent lanes (a DPP quad at most) share the products of a table row
     int lk_row;       // FPMul's lk1, Mul's lk: while the t + 2 rows fit half a wave
-    int lk_wave;      // FPMul's lk3, TruncPr's lk: while the t + 1 rows fit the wave
+    int lk_wave;      // FPMul's lk3, TruncPr's and Input's lk: while the t + 1 rows fit the wave
     bool pair_first;  // FPMul, Mul: the separate launches offer the open of a - x and b - y to the decode's pair form first
 };
 
@@ -59,6 +61,7 @@ inline ProtocolPlan plan_protocol(const ProtocolKnobs& k, const ProtocolShape& s
         // a chunk is t + 1 elements; both opens decode from exactly 2t + 1 senders, and the pairs of one open fit the workgroup
         one = any && k.impl != IMPL_SAT32 && s.N / (s.t + 1) <= k.fused_randbit_max && s.n <= 16 && s.t >= 1;
         break;
+    case ProtocolCall::Input: one = wave && s.N <= k.fused_input_max; break;
     }
     // the pair form: ahead from ~8 000 elements (tools/sweep_fused_fpmul.py); Goldilocks has none
     return ProtocolPlan{one, lane_share(s.t + 2, 32, s.t), lane_share(s.t + 1, 64, s.t), (fpmul || mul) && !gold && s.N >= k.pair_decode_min};

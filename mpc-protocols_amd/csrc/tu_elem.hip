@@ -68,6 +68,10 @@ void launch_truncpr_finalize(int impl, const uint32_t* a, const uint32_t* r_dash
                              const ElemConsts& cs, uint32_t* d_out, hipStream_t s) {
     by_fr_impl(impl, [&](auto f) { hipLaunchKernelGGL((k_truncpr_finalize<field_t<decltype(f)>>), elem_grid(N, parties), dim3(256), 0, s, a, r_dash, c_open, m, N, cs, d_out); });
 }
+void launch_input_finish(int impl, const uint8_t* status, uint32_t* mask, const uint32_t* x, const uint32_t* r, size_t N, unsigned parties, uint32_t* masked,
+                         uint32_t* in_sh, hipStream_t s) {
+    by_field(impl, [&](auto f) { hipLaunchKernelGGL((k_input_finish<field_t<decltype(f)>>), elem_grid(N, parties + 1), dim3(256), 0, s, status, mask, x, r, N, masked, in_sh); });
+}
 void launch_modmul_ubench(int impl, uint32_t* out, size_t threads, uint32_t iters, const ElemConsts& cs, hipStream_t s) {
     by_fr_impl(impl, [&](auto f) { hipLaunchKernelGGL((k_modmul_ubench<field_t<decltype(f)>>), elem_grid(threads), dim3(256), 0, s, out, iters, cs); });
 }

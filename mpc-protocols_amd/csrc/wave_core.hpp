@@ -1,6 +1,7 @@
 // The pieces that the one-launch protocol kernels are composed of: k_mul_wave and k_truncpr_wave (a wave per batch element) use
-// all of them, k_fpmul_wave the opens, the last step and the LDS element helpers (its staging and products are written out there,
-// kernels_fpmul_wave.hpp says why), k_triplegen_wg, k_randbit_wg and k_prandbit_wg (a workgroup per chunk) the LDS element helpers.
+// all of them, k_input_wave the table stage and the single open, k_fpmul_wave the opens, the last step and the LDS element helpers
+// (its staging and products are written out there, kernels_fpmul_wave.hpp says why), k_triplegen_wg, k_randbit_wg and k_prandbit_wg
+// (a workgroup per chunk) the LDS element helpers.
 // The summary tail is finish_direct (kernels_recover.hpp); k_fpmul_wave and k_randbit_wg keep theirs written out.
 //
 // LDS layout the wave kernels share: canonical operands are 8 words apart, limb-form values (U29) 12.  12 is 16-byte aligned, and
@@ -174,8 +175,9 @@ HB_DEV void open_pair(const uint32_t* ysd, const uint32_t* yse, const uint32_t* 
 
 // TruncPr's open (truncpr.rs:215) of chunk g: party p's share as limbs at val + p * 12, the senders picked by `rows`.  Row nv:
 // P(0).  Leaves the opened value as canonical words at `opened`; it goes to c_open[g], the status byte to status[g] (or null).
+// Returns whether the chunk verified, the same in every lane (Input's last step must not run on a zero that stands for a failure).
 template <class F>
-HB_DEV void open_single(const uint32_t* val, const uint32_t* tab, uint32_t* opened, int lk, int nv, int M, const RowsArg& rows, bool live,
+HB_DEV bool open_single(const uint32_t* val, const uint32_t* tab, uint32_t* opened, int lk, int nv, int M, const RowsArg& rows, bool live,
                         size_t g, uint32_t* counters, uint32_t* c_open, uint8_t* status) {
     using E = typename F::E;
     const int lane = threadIdx.x & 63;
@@ -199,6 +201,7 @@ HB_DEV void open_single(const uint32_t* val, const uint32_t* tab, uint32_t* open
             }
         }
     }
+    return ok;
 }
 
 // ---- a product per lane: res = sum_k op_k c_k with one reduction ("sum of a_k * c_k, then one REDC": the lanes stay converged) ---

@@ -76,6 +76,7 @@ def riss_tsets(n, t):
 
 FUSED_TRUNCPR_DEFAULT = 768  # hbmpc_set_fused_truncpr's default (csrc/hbmpc_capi.hip)
 FUSED_MUL_DEFAULT = 1024  # hbmpc_set_fused_mul's default (csrc/hbmpc_capi.hip)
+FUSED_INPUT_DEFAULT = 768  # hbmpc_set_fused_input's default (csrc/hbmpc_capi.hip)
 FUSED_RANDBIT_DEFAULT = {"fr": 256, "goldilocks": 1024}  # hbmpc_set_fused_randbit's default per field (FUSED_RANDBIT_FR / _GL, csrc/hbmpc_capi.hip)
 FUSED_PRANDBIT_DEFAULT = 256  # hbmpc_set_fused_prandbit's default (FUSED_PRANDBIT, csrc/hbmpc_capi.hip)
 
@@ -605,6 +606,26 @@ class Engine:
     def set_fused_mul(self, max_elements: int):
         """hbmpc_dev_mul_parties is one launch up to this many batch elements (0: always three)"""
         assert self.L.hbmpc_set_fused_mul(self.ctx, C.c_size_t(max_elements)) == 0
+
+    def input_parties(self, sender_ids, x_d, r_d, N, n, t, mask_d, masked_d, in_sh_d, status_d, summary_d=0, stream=0):
+        """Input for all n parties of this device in one call (hbmpc_[gl_]dev_input_parties; sender_ids are party ids): the client's open
+        of the masks, masked = x + mask, in_sh[p] = masked - r[p]; an element whose mask does not open (status >= 2) is refused: zeros,
+        never x + 0.  Over Fr one launch for a small batch, two otherwise; returns the ShareErrorCode"""
+        ids = (C.c_size_t * len(sender_ids))(*sender_ids)
+        return self._f("dev_input_parties")(self.ctx, ids, C.c_size_t(len(sender_ids)), C.c_void_p(x_d), C.c_void_p(r_d), C.c_size_t(N),
+                                            C.c_size_t(n), C.c_size_t(t),
+                                            *(C.c_void_p(p) for p in (mask_d, masked_d, in_sh_d, status_d, summary_d)), C.c_void_p(stream))
+
+    def output_parties(self, sender_ids, sh_d, N, n, t, out_d, status_d=0, summary_d=0, stream=0):
+        """Output's client side (hbmpc_[gl_]dev_output_parties; sender_ids are party ids): the P(0) decode of degree t of the senders'
+        rows of sh [party][N], read in place; returns the ShareErrorCode"""
+        ids = (C.c_size_t * len(sender_ids))(*sender_ids)
+        return self._f("dev_output_parties")(self.ctx, ids, C.c_size_t(len(sender_ids)), C.c_void_p(sh_d), C.c_size_t(N), C.c_size_t(n),
+                                             C.c_size_t(t), *(C.c_void_p(p) for p in (out_d, status_d, summary_d)), C.c_void_p(stream))
+
+    def set_fused_input(self, max_elements: int):
+        """hbmpc_dev_input_parties is one launch up to this many batch elements (0: always two)"""
+        assert self.L.hbmpc_set_fused_input(self.ctx, C.c_size_t(max_elements)) == 0
 
     def dev_beaver_open_shares_paired(self, a_d, b_d, x_d, y_d, N, parties, de_d, stream=0):
         """de[party][0][N] = a - x, de[party][1][N] = b - y: one P(0) decode over 2 N values per sender opens both"""

@@ -14,6 +14,9 @@ in the library; this file only names things for the tests and bench.py.
   Preprocessing  run_preprocessing's triple part (honeybadger/mod.rs:1239-1393): RanSha -> a, b; RanDouSha -> r; TripleGen
   Mul            Multiply (Beaver, RBC path): the opened shares, the open, finalize_mul
                  honeybadger/mod.rs:543-628, mul/multiplication.rs:417-426,102-139,57-100
+  Input          the client's open of the masks, masked = x + mask, the servers' masked - r
+                 honeybadger/input/input.rs:489-506, 85-100, 300-301
+  Output         the client's open of the result shares                      honeybadger/output/output.rs:157-177
   TruncPr        TruncPrNode on its own                                      fpmul/truncpr.rs:185-318
   FpDivConst     FPDivConstNode: a * w for a public reciprocal w, then TruncPr   fpdiv/fpdiv_const.rs:61-99, fpdiv/mod.rs:8-60
   RandBit        RandBit: Beaver square of a, BatchRecon of a^2, phase 2   fpmul/rand_bit.rs:242-293,197-220
@@ -174,6 +177,44 @@ class Mul(_Pipe):
     def download(self, which="out"):
         shape = {"deop": (2 * self.N,), "dop": (self.N,), "eop": (self.N,), "desh": (self.n, 2, self.N)}.get(which, (self.n, self.N))
         return self.download_named(which, shape)
+
+
+class Input(_Pipe):
+    """Input (honeybadger/input/input.rs:489-506, 85-100, 300-301) of N client values for n parties, in either field: the masks are
+    opened from parties 0 .. open_senders - 1 (default 2t + 1), masked = x + mask, out[p] = masked - r[p].  Buffers x, mask, masked
+    are [N], r and out [party][N], status N bytes, summary the open's.  An element whose mask does not open is refused: zeros in mask,
+    masked and out, never x + 0; run(check=True) then raises where the reference's `?` returns the error.  run() is one library call
+    (hbmpc_[gl_]dev_input_parties): over Fr ONE launch up to hbmpc_set_fused_input elements when the open has exactly 2t + 1 senders,
+    two launches otherwise."""
+
+    def __init__(self, eng, n, t, N, stream=0, open_senders=None):
+        self.n, self.t, self.N = n, t, N
+        self.open_senders = 2 * t + 1 if open_senders is None else open_senders
+        super().__init__(eng, self._create(eng, "hbmpc_pipe_input_create", n, t, N, self.open_senders, stream=stream), stream)
+
+    def upload(self, x, r):
+        self.upload_named("x", x)
+        self.upload_named("r", r)
+
+    def download(self, which="out"):
+        return self.download_named(which, (self.n, self.N) if which in ("out", "r") else (self.N,))
+
+
+class Output(_Pipe):
+    """Output (honeybadger/output/output.rs:157-177) of N result values from n parties' shares sh [party][N], in either field: out [N]
+    is the P(0) decode of degree t from parties 0 .. open_senders - 1 (default 2t + 1); status N bytes, summary the open's.  run() is
+    one library call (hbmpc_[gl_]dev_output_parties); run(check=True) raises where the reference's first error aborts."""
+
+    def __init__(self, eng, n, t, N, stream=0, open_senders=None):
+        self.n, self.t, self.N = n, t, N
+        self.open_senders = 2 * t + 1 if open_senders is None else open_senders
+        super().__init__(eng, self._create(eng, "hbmpc_pipe_output_create", n, t, N, self.open_senders, stream=stream), stream)
+
+    def upload(self, sh):
+        self.upload_named("sh", sh)
+
+    def download(self, which="out"):
+        return self.download_named(which, (self.n, self.N) if which == "sh" else (self.N,))
 
 
 class TruncPr(_Pipe):

@@ -320,6 +320,19 @@ impl GpuShares {
         let rc = unsafe { sys::hbmpc_pipe_mul_create(self.ctx, n, t, pairs, 0, stream, &mut p) };
         self.wrap(rc, p, n)
     }
+    /// Input for all n parties (honeybadger/input/input.rs:489-506, 85-100, 300-301): buffers x ([values]), r ([party][values], the shares
+    /// of the masks); mask, masked ([values]), out = the shares of x.  A mask that does not open refuses its element (zeros, never x + 0)
+    pub fn pipe_input(&self, n: usize, t: usize, values: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_input_create(self.ctx, n, t, values, 0, stream, &mut p) };
+        self.wrap(rc, p, n)
+    }
+    /// Output's client side for all n parties' result shares (honeybadger/output/output.rs:157-177): buffer sh ([party][values]), out ([values])
+    pub fn pipe_output(&self, n: usize, t: usize, values: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_output_create(self.ctx, n, t, values, 0, stream, &mut p) };
+        self.wrap(rc, p, n)
+    }
     /// `TruncPrNode` on its own for all n parties (fpmul/truncpr.rs:185-318): buffers a, rint ([party][values]), rbits ([party][m][values])
     pub fn pipe_truncpr(&self, n: usize, t: usize, values: usize, k: usize, m: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
         let mut p = std::ptr::null_mut();
