@@ -3,6 +3,7 @@
 #include "fr_gold.hpp"
 #include "kernels_eval.hpp"
 #include "launchers.hpp"
+#include "wide_plan.hpp"
 namespace hbmpc {
 // a run-time flag as a compile-time one: fn(std::true_type{}) or fn(std::false_type{})
 template <class Fn>
@@ -31,20 +32,6 @@ void launch_recover_generic(int impl, bool p0, const RecoverArgs& ra, unsigned g
         by_bool(p0, [&](auto P0) { hipLaunchKernelGGL((k_batch_recover_generic<F, decltype(P0)::value>), dim3(grid), dim3(256), 0, s, ra); });
     });
 }
-// LDS of one workgroup of k_batch_recover_wide; *tab_words = 0 when the call's table cannot be staged (not contiguous, or
-// beyond what a launch may ask for without raising the function's limit)
-static size_t wide_lds(int impl, const RecoverArgs& ra, bool p0, int ow_sel, int* tab_words, int* split) {
-    const size_t ew = impl_ebytes(impl) / 4, nl = (size_t)impl_nl(impl);
-    const size_t nv = (size_t)(ra.needed - ra.m), ow = p0 ? 1 : ow_sel ? (size_t)ow_sel : (size_t)ra.m;
-    const size_t front = 4 * (size_t)ra.needed * ew * 4;
-    const size_t tw = (nv + ow) * (size_t)ra.m * nl;
-    const bool fits = front + tw * 4 <= 64 * 1024;
-    const bool contiguous = ra.bc == ra.vm + nv * (size_t)ra.m * nl && ((uintptr_t)ra.vm & 15) == 0;
-    const bool staged = fits && (contiguous || p0);  // a single output row elsewhere in the table (one coefficient): staged from both ranges
-    *split = staged && !contiguous ? 1 : 0;
-    *tab_words = staged ? (int)tw : 0;
-    return front + (staged ? tw * 4 : 0);
-}
 void launch_recover_wide(int impl, bool p0, const RecoverArgs& ra, const SecondArgs* sc, hipStream_t s, int ow_sel) {
     const unsigned grid = (unsigned)((ra.G + 3) / 4);
     WideArgs wa;
@@ -53,13 +40,11 @@ void launch_recover_wide(int impl, bool p0, const RecoverArgs& ra, const SecondA
     if (sc) wa.sc = *sc;
     else memset(&wa.sc, 0, sizeof wa.sc);
     wa.ow = p0 ? 0 : ow_sel;
-    const size_t lds = wide_lds(impl, ra, p0, ow_sel, &wa.tab_words, &wa.split);
+    const size_t nv = (size_t)(ra.needed - ra.m);
+    const WidePlan wp = wide_plan(impl, ra.needed, ra.m, p0, ow_sel, ra.bc == ra.vm + nv * (size_t)ra.m * (size_t)impl_nl(impl), ((uintptr_t)ra.vm & 15) == 0);
+    const size_t lds = wp.lds;
+    wa.tab_words = wp.tab_words, wa.split = wp.split, wa.lk = wp.lk;
     const bool tab = wa.tab_words != 0;
-    wa.lk = 0;
-    if (tab && impl == IMPL_U29) {  // a row's products shared by up to four lanes while every row still fits the wave (dot_shared)
-        const int rows = (ra.needed - ra.m) + (p0 ? 1 : ow_sel ? ow_sel : ra.m);
-        while (wa.lk < 2 && (rows << (wa.lk + 1)) <= 64 && (2 << wa.lk) <= ra.m) ++wa.lk;
-    }
     by_field(impl, [&](auto f) {
         using F = typename decltype(f)::type;
         by_bool(p0, [&](auto P0) {

@@ -5,6 +5,8 @@
 //   usage: host_tables_dump <fr|gl> <n> <d> <t> <id0,id1,...> [full]
 //          host_tables_dump sqrt <fr-u29|fr-sat32|gl>          build_sqrt_table: a line "sqrt <layout numbers>", then the words
 //          host_tables_dump riss <fr|fr-sat32|gl> <n> <t> <own|-1>   build_riss_table: a line "riss <layout numbers>", then the words
+// The share tables' lines end with "recover_vm" / "recover_bc" (build_recover_tables: the optimistic decode's verify and coefficient rows in
+// the device-constant form) and, with OEC rounds, "second" (build_second_tables).
 // (the words of these two modes follow their line as raw little-endian 32-bit values: the tables reach tens of megabytes)
 // full: the matrix-core tables are printed whatever their size, and so are the tables of the other instances -- enc (one row per point),
 // bflyR (point pairs, rows alpha^i 2^261: triple generation), bflyinv (point pairs of the inverse transform on a full domain)
@@ -58,6 +60,12 @@ static int run(size_t n, size_t d, size_t t, const std::vector<size_t>& ids, boo
     std::printf("const");
     for (uint32_t x : words) std::printf(" %08x", x);
     std::printf("\n");
+    // the optimistic decode's tables as the kernels read them (build_recover_tables): verify rows, then coefficient rows
+    {
+        const RecoverTables T = build_recover_tables<H>(ids, n, d, t, std::is_same<H, HGl>::value ? IMPL_GOLD : IMPL_U29);
+        put_words("recover_vm", T.vm);
+        put_words("recover_bc", T.bc);
+    }
     // the second-chance tables (k_second_chance): window offsets, then every table word in the device-constant form
     const size_t S = ids.size(), rmax = S > needed ? (t < S - needed ? t : S - needed) : 0;
     if (rmax >= 1) {
