@@ -237,6 +237,15 @@ ShareErrorCode hbmpc_pipe_input_create(hbmpc_ctx* ctx, size_t n, size_t t, size_
  * hbmpc_dev_output_parties / hbmpc_gl_dev_output_parties, senders and checking as in input.  Buffers: sh (input [n][N]); out ([N]);
  * status (N bytes); summary. */
 ShareErrorCode hbmpc_pipe_output_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t open_senders, void* stream, hbmpc_pipe** pipe_out);
+/* BatchRecon (honeybadger/batch_recon/batch_recon.rs:144-185, 371-391, 451-467) of N shared values of degree d for n parties, over
+ * either field: opened = the N values, through the reference's two arms.  run() is hbmpc_dev_batchrecon_parties /
+ * hbmpc_gl_dev_batchrecon_parties with parties 0 .. eval_senders - 1 and 0 .. reveal_senders - 1 as the two sender sets (0: d + t + 1);
+ * checked, it returns the first failing decode's error.  deal() is the EvalBatch arm alone (the encode and the recipients' decodes up to
+ * Z), finish() the RevealBatch arm (the decode of Z), as separate launches: a caller may rewrite rows of Z in between.
+ * Buffers: x (input [n][N]); Y ([n][n][G]), Z ([n][G]), opened ([N]); rstatus (n G bytes), status (G bytes), G = N / (d + 1);
+ * summary_first, summary. */
+ShareErrorCode hbmpc_pipe_batchrecon_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t d, size_t N, size_t eval_senders, size_t reveal_senders,
+                                            void* stream, hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_ransha_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t K, size_t verify_senders, void* stream,
                                         hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_randousha_create(hbmpc_ctx* ctx, size_t n, size_t t, size_t K, void* stream, hbmpc_pipe** pipe_out);
@@ -655,6 +664,35 @@ ShareErrorCode hbmpc_dev_input_parties(hbmpc_ctx* ctx, const size_t* sender_ids,
 ShareErrorCode hbmpc_gl_dev_input_parties(hbmpc_ctx* ctx, const size_t* sender_ids, size_t S, const uint64_t* x, const uint64_t* r_sh, size_t N,
                                           size_t n, size_t t, uint64_t* mask_out, uint64_t* masked_out, uint64_t* in_sh_out, uint8_t* status_out,
                                           hbmpc_recover_summary* summary_dev, void* stream);
+/* BatchReconNode (honeybadger/batch_recon/batch_recon.rs) for a device that holds every party's shares: the public BatchRecPub of
+ * N = G (d + 1) shared values of degree d, opened to all parties through the reference's two arms.
+ *   x           [party][N]            the parties' shares, in chunks of d + 1 (init_batch_reconstruct_many, :144-185)
+ *   y_ws        [party][recipient][G] the EvalBatch messages: y = sum_k alpha_recipient^k x_party[chunk][k]
+ *   z_out       [recipient][G]        the RevealBatch messages: recipient j's P(0) decode of the eval senders' y (:371-391)
+ *   opened_out  [G][d + 1] = [N]      the opened values in the order of x: the coefficient decode of the reveal senders' z (:451-467)
+ *   rstatus_out [n G]                 byte j G + g: recipient j's decode of chunk g;  status_out [G]: the decode of the revealed values
+ * eval_senders[S1] and reveal_senders[S2] are PARTY ids in any order, distinct and below n, d + t + 1 <= S <= n each: the parties whose
+ * messages everyone decodes from (a live node acts on the first d + t + 1 to arrive).  They need not be prefixes or equal.
+ * Every buffer, status byte and summary holds exactly what hbmpc_dev_vandermonde_apply_parties (x -> y_ws),
+ * hbmpc_dev_batch_recover_slots in its P(0) form (ids and slots eval_senders, evals y_ws, row_stride n G, n G chunks -> z_out,
+ * rstatus_out, summary_first_dev; all n recipients) and hbmpc_dev_batch_recover_slots in its coefficient form (ids and slots
+ * reveal_senders, evals z_out, G chunks -> opened_out, status_out, summary_dev) leave, in this order.  A chunk that fails a decode
+ * gives zeros and is counted, and the next step runs on that zero; with S > d + t + 1 a decode is robust (OEC / Gao fallback).
+ * rstatus_out, status_out and the two summaries may be null.
+ * InvalidInput, before the first launch (a refused call has written nothing): a null required buffer, N == 0 or N % (d + 1) != 0, d == 0,
+ * n == 0 or n > 255, n < 3t + 1, S < d + t + 1, a duplicate or out-of-range id.  TypeMismatch: the Fr call on a Goldilocks context and
+ * the other way round.
+ * With S1 == S2 == d + t + 1, n <= 16 and at most hbmpc_set_fused_batchrecon chunks the call is ONE launch, a workgroup per chunk
+ * (csrc/kernels_batchrecon_wg.hpp; a Sat32 context never takes it); otherwise the three launches above.  Same bytes in either form.
+ * Not here: sessions, the bincode envelope, the ark Vec<F> payloads (hbmpc_dev_encode_fvec / _validate_fvec), per-recipient sender sets. */
+ShareErrorCode hbmpc_dev_batchrecon_parties(hbmpc_ctx* ctx, const size_t* eval_senders, size_t S1, const size_t* reveal_senders, size_t S2,
+                                            const U256* x, size_t N, size_t n, size_t d, size_t t, U256* y_ws, U256* z_out, U256* opened_out,
+                                            uint8_t* rstatus_out, uint8_t* status_out, hbmpc_recover_summary* summary_first_dev,
+                                            hbmpc_recover_summary* summary_dev, void* stream);
+ShareErrorCode hbmpc_gl_dev_batchrecon_parties(hbmpc_ctx* ctx, const size_t* eval_senders, size_t S1, const size_t* reveal_senders, size_t S2,
+                                               const uint64_t* x, size_t N, size_t n, size_t d, size_t t, uint64_t* y_ws, uint64_t* z_out,
+                                               uint64_t* opened_out, uint8_t* rstatus_out, uint8_t* status_out,
+                                               hbmpc_recover_summary* summary_first_dev, hbmpc_recover_summary* summary_dev, void* stream);
 /* Output's client side for a device that holds every party's result shares (honeybadger/output/output.rs:157-177):
  * recover_secret(.., n, t) per element.  sh is [party][N], sender_ids[S] PARTY ids, out [N]; out, status_out[N] and summary_dev (either
  * may be null) hold exactly what hbmpc_dev_batch_recover_p0 leaves for G = N, d = t from the senders' rows, which are read in place
@@ -1125,6 +1163,9 @@ ShareErrorCode hbmpc_set_fused_mul(hbmpc_ctx* ctx, size_t max_elements);
 /* hbmpc_dev_input_parties runs as one launch up to max_elements batch elements (default 768; 0: always the two separate
  * launches).  Same bytes either way (A/B aid). */
 ShareErrorCode hbmpc_set_fused_input(hbmpc_ctx* ctx, size_t max_elements);
+/* hbmpc_[gl_]dev_batchrecon_parties runs as one launch up to max_chunks chunks of d + 1 elements (default 512 over Fr, 256 over
+ * Goldilocks; 0: always the three separate launches).  Same bytes either way (A/B aid). */
+ShareErrorCode hbmpc_set_fused_batchrecon(hbmpc_ctx* ctx, size_t max_chunks);
 /* hbmpc_[gl_]dev_randbit_parties runs as one launch up to max_chunks chunks of t + 1 elements (default 256 over Fr, 1024 over
  * Goldilocks; 0: always the nine separate launches).  Same bytes either way (A/B aid). */
 ShareErrorCode hbmpc_set_fused_randbit(hbmpc_ctx* ctx, size_t max_chunks);

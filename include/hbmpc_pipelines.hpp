@@ -12,6 +12,7 @@
 //                  honeybadger/mod.rs:543-628, mul/multiplication.rs:417-426,102-139,57-100
 //   Input          the client's open of the masks, masked = x + mask, the servers' masked - r
 //                  honeybadger/input/input.rs:489-506, 85-100, 300-301
+//   BatchRecon     the public open of a vector of shared values through both arms  batch_recon/batch_recon.rs:144-185, 371-391, 451-467
 //   Output         the client's open of the result shares                           honeybadger/output/output.rs:157-177
 //   TruncPr        TruncPrNode on its own                                           fpmul/truncpr.rs:185-318
 //   FpDivConst     FPDivConstNode: a * w for a public reciprocal w, then TruncPr    fpdiv/fpdiv_const.rs:61-99, fpdiv/mod.rs:8-60
@@ -177,6 +178,38 @@ class Output : public Pipeline {
     static hbmpc_pipe* create(hbmpc_ctx* ctx, size_t n, size_t t, size_t N, size_t open_senders, void* stream) {
         hbmpc_pipe* h = nullptr;
         pl_check(hbmpc_pipe_output_create(ctx, n, t, N, open_senders, stream, &h), ctx, "hbmpc_pipe_output_create");
+        return h;
+    }
+};
+
+// BatchRecon (honeybadger/batch_recon/batch_recon.rs:144-185, 371-391, 451-467) of N = G (d + 1) shared values of degree d for n parties
+// over Fr: opened = the N values, through the reference's two arms.  eval_senders / reveal_senders: parties 0 .. S - 1 whose messages
+// everyone decodes from (0 = d + t + 1).  deal() / finish() are the two arms as separate launches: rows of Z may be rewritten in
+// between.  A checked run() throws at the first failing decode.  (A Goldilocks context takes the same handle through the C ABI; this
+// class names its buffers as U256.)
+class BatchRecon : public Pipeline {
+  public:
+    BatchRecon(hbmpc_ctx* ctx, size_t n, size_t t, size_t d, size_t N, void* stream, size_t eval_senders = 0, size_t reveal_senders = 0)
+        : Pipeline(ctx, create(ctx, n, t, d, N, eval_senders, reveal_senders, stream), stream) {
+        x = buffer("x"), Y = buffer("Y"), Z = buffer("Z"), opened = buffer("opened");
+        rstatus = reinterpret_cast<uint8_t*>(buffer("rstatus")), status = reinterpret_cast<uint8_t*>(buffer("status"));
+    }
+    U256* x;                    // [party][N]
+    U256 *Y, *Z, *opened;       // [party][recipient][G]; [recipient][G]; [N]
+    uint8_t *rstatus, *status;  // [n G], [G]
+    void deal(bool checked = false) {
+        pl_check(hbmpc_pipe_set_checked(h_, checked ? 1 : 0), ctx_, "set_checked");
+        pl_check(hbmpc_pipe_deal(h_), ctx_, "deal");
+    }
+    void finish(bool checked = false) {
+        pl_check(hbmpc_pipe_set_checked(h_, checked ? 1 : 0), ctx_, "set_checked");
+        pl_check(hbmpc_pipe_finish(h_), ctx_, "finish");
+    }
+
+  private:
+    static hbmpc_pipe* create(hbmpc_ctx* ctx, size_t n, size_t t, size_t d, size_t N, size_t eval_senders, size_t reveal_senders, void* stream) {
+        hbmpc_pipe* h = nullptr;
+        pl_check(hbmpc_pipe_batchrecon_create(ctx, n, t, d, N, eval_senders, reveal_senders, stream, &h), ctx, "hbmpc_pipe_batchrecon_create");
         return h;
     }
 };

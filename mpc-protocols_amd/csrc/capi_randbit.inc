@@ -20,15 +20,9 @@ struct RandBitCall {
 ShareErrorCode randbit_launches(hbmpc_ctx* ctx, const RandBitCall& c) {
     const size_t N = c.N, n = c.n, t = c.t, Gde = 2 * N / (t + 1), Gsq = N / (t + 1), eb = ebytes(ctx);
     const std::vector<size_t> ids = first_ids(2 * t + 1);
-    // BatchRecon (degree t) of x [party][G (t + 1)] -> opened [G (t + 1)] (batch_recon.rs:157-165, 384-391, 457-467)
+    // BatchRecon (degree t) of x [party][G (t + 1)] -> opened [G (t + 1)]: the three launches of capi_batchrecon.inc from senders 0 .. 2t
     auto open = [&](const void* x, size_t G, void* opened, uint8_t* st, hbmpc_recover_summary* first, hbmpc_recover_summary* second) -> ShareErrorCode {
-        ShareErrorCode rc = eval_dev(ctx, x, G, n, t, c.Y, c.stream, n);
-        if (rc != ShareSuccess) return rc;
-        rc = batch_recover_dev(ctx, {.sender_ids = ids.data(), .S = ids.size(), .evals = c.Y, .row_stride = n * G, .G = n * G, .n = n, .d = t, .t = t,
-                                     .out = c.Z, .status = st, .summary = first, .p0 = true, .stream = c.stream, .honest_majority = true});
-        if (rc != ShareSuccess) return rc;
-        return batch_recover_dev(ctx, {.sender_ids = ids.data(), .S = ids.size(), .evals = c.Z, .G = G, .n = n, .d = t, .t = t, .out = opened, .status = st,
-                                       .summary = second, .stream = c.stream, .honest_majority = true});
+        return batchrecon_launches(ctx, ids.data(), ids.size(), ids.data(), ids.size(), x, G, n, t, t, c.Y, c.Z, opened, st, st, first, second, c.stream, true);
     };
     // Multiply::init(a, a, triples): d = ta - a, e = tb - a (multiplication.rs:417-426), opened together
     ShareErrorCode rc = beaver_open_pair_any(ctx, c.ta, c.tb, c.a, c.a, N, n, c.desh, c.stream);

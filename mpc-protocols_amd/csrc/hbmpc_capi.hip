@@ -24,6 +24,7 @@
 #include "kernels_input_wave.hpp"
 #include "kernels_triplegen_wg.hpp"
 #include "kernels_randbit_wg.hpp"
+#include "kernels_batchrecon_wg.hpp"
 #include "kernels_prandbit_wg.hpp"
 #include "bfly_ring_plan.hpp"
 #include "launchers.hpp"
@@ -49,6 +50,10 @@ constexpr size_t FUSED_RANDBIT_FR = 256, FUSED_RANDBIT_GL = 1024;
 // elements -- the largest swept count at which one launch was not slower than the composition of eight calls at (7,2) and at (10,3)
 // (profiles/fused_prandbit_sweep.txt)
 constexpr size_t FUSED_PRANDBIT = 256;
+// hbmpc_[gl_]dev_batchrecon_parties as one launch: the defaults of hbmpc_set_fused_batchrecon per field, in chunks of d + 1 elements --
+// the largest swept count at which one launch was not slower than the three launches at (4, 1, d = 1), (16, 5, d = 5) and
+// (16, 5, d = 10), eager and replayed (profiles/fused_batchrecon_sweep.txt)
+constexpr size_t FUSED_BATCHRECON_FR = 512, FUSED_BATCHRECON_GL = 256;
 constexpr size_t STAGE_PIN_BLOCK = (size_t)2048 << 10;  // pinned host block of the small-call staging path (Stage, hbmpc_scrub_staging)
 struct hbmpc_ctx {
     int device = 0;
@@ -90,6 +95,7 @@ struct hbmpc_ctx {
     size_t fused_mul_max = 1024;                   // hbmpc_dev_mul_parties: the same (profiles/fused_mul_sweep.txt: ahead both eager and replayed)
     size_t fused_input_max = 768;                  // hbmpc_dev_input_parties: the same (profiles/fused_input_sweep.txt)
     size_t fused_randbit_max = FUSED_RANDBIT_FR;   // hbmpc_dev_randbit_parties: one launch (a workgroup per chunk of t + 1 elements) up to this many chunks (0: never); per field, hbmpc_create
+    size_t fused_batchrecon_max = FUSED_BATCHRECON_FR;  // hbmpc_dev_batchrecon_parties: one launch (a workgroup per chunk of d + 1 elements) up to this many chunks (0: never); per field, hbmpc_create
     size_t fused_prandbit_max = FUSED_PRANDBIT;    // hbmpc_dev_prandbit_parties / _prandint_parties (read from the Fr context): the same, in chunks of t + 1 elements
     bool gather_row_copies = false;                // hbmpc_dev_gather_party_major: take the per-row peer copies even where the 2-D copy applies (A/B aid)
     bool list_rows_in_kernel = true;               // the producers' mixing step writes the parties' lists itself (k_mfma_bfly<.., LISTS>)
@@ -386,7 +392,7 @@ extern "C" ShareErrorCode hbmpc_create(int device, FieldKind field_kind, hbmpc_c
     }
     const char* env = getenv("HBMPC_FIELD_IMPL");
     if (env && std::string(env) == "sat32") ctx->impl = IMPL_SAT32;
-    if (field_kind == Goldilocks64) ctx->impl = IMPL_GOLD, ctx->fused_randbit_max = FUSED_RANDBIT_GL;
+    if (field_kind == Goldilocks64) ctx->impl = IMPL_GOLD, ctx->fused_randbit_max = FUSED_RANDBIT_GL, ctx->fused_batchrecon_max = FUSED_BATCHRECON_GL;
     env = getenv("HBMPC_MATRIX_CORES");
     if (env && std::string(env) == "0") ctx->matrix_cores = false;
     hipDeviceProp_t prop;
@@ -461,6 +467,7 @@ KNOB_SETTER(hbmpc_set_fused_triplegen, fused_triplegen_max)
 KNOB_SETTER(hbmpc_set_fused_mul, fused_mul_max)
 KNOB_SETTER(hbmpc_set_fused_input, fused_input_max)
 KNOB_SETTER(hbmpc_set_fused_randbit, fused_randbit_max)
+KNOB_SETTER(hbmpc_set_fused_batchrecon, fused_batchrecon_max)
 KNOB_SETTER(hbmpc_set_fused_prandbit, fused_prandbit_max)
 KNOB_SETTER(hbmpc_set_fpmul_pair_decode, pair_decode_min)
 #undef KNOB_SETTER
@@ -2295,5 +2302,6 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
 #include "capi_truncpr.inc"
 #include "capi_mul.inc"
 #include "capi_input.inc"
+#include "capi_batchrecon.inc"
 #include "capi_randbit.inc"
 #include "capi_prandbit.inc"

@@ -120,6 +120,10 @@ struct TripleGenWgArgs;
 void launch_triplegen_wg(int impl, const TripleGenWgArgs& a, hipStream_t s);  // TripleGenNode, a workgroup per chunk (kernels_triplegen_wg.hpp): U29 or Goldilocks
 struct RandBitWgArgs;
 void launch_randbit_wg(int impl, const RandBitWgArgs& a, hipStream_t s);  // RandBit, a workgroup per chunk of t + 1 elements (kernels_randbit_wg.hpp): U29 or Goldilocks
+// BatchReconNode, a workgroup per chunk of d + 1 elements (kernels_batchrecon_wg.hpp): U29 or Goldilocks.  false: no kernel over this
+// field, the layout does not fit a workgroup's LDS or the LDS attribute could not be set; dry_run: only say which
+struct BatchReconWgArgs;
+bool launch_batchrecon_wg(int impl, const BatchReconWgArgs& a, int device, hipStream_t s, bool dry_run);
 bool launch_fpmul_wave(const FpmulWaveArgs& a, int device, hipStream_t s, bool dry_run);
 // TruncPrNode / FPDivConstNode (a.w set) the same way (kernels_truncpr_wave.hpp); dry_run: only say whether the LDS layout fits
 struct TruncprWaveArgs;

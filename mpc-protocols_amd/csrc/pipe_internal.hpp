@@ -74,6 +74,17 @@ struct Calls {
                   : hbmpc_dev_mul_parties(c, ids, S, (const F*)ta, (const F*)tb, (const F*)tc, (const F*)x, (const F*)y, N, n, t, (F*)desh, (F*)deop,
                                           (F*)out, st, sm, s);
     }
+    ShareErrorCode batchrecon_parties(hbmpc_ctx* c, const size_t* ids1, size_t S1, const size_t* ids2, size_t S2, const void* x, size_t N, size_t n,
+                                      size_t d, size_t t, void* Y, void* Z, void* opened, uint8_t* rst, uint8_t* st, hbmpc_recover_summary* sf,
+                                      hbmpc_recover_summary* sm, void* s) const {
+        return gl ? hbmpc_gl_dev_batchrecon_parties(c, ids1, S1, ids2, S2, (const G*)x, N, n, d, t, (G*)Y, (G*)Z, (G*)opened, rst, st, sf, sm, s)
+                  : hbmpc_dev_batchrecon_parties(c, ids1, S1, ids2, S2, (const F*)x, N, n, d, t, (F*)Y, (F*)Z, (F*)opened, rst, st, sf, sm, s);
+    }
+    ShareErrorCode recover_slots(hbmpc_ctx* c, const size_t* ids, size_t S, const void* ev, size_t stride, size_t B, size_t n, size_t d, size_t t,
+                                 int p0_only, void* out, uint8_t* st, hbmpc_recover_summary* sm, void* s) const {
+        return gl ? hbmpc_gl_dev_batch_recover_slots(c, ids, ids, S, (const G*)ev, stride, B, n, d, t, p0_only, (G*)out, nullptr, st, sm, s)
+                  : hbmpc_dev_batch_recover_slots(c, ids, ids, S, (const F*)ev, stride, B, n, d, t, p0_only, (F*)out, nullptr, st, sm, s);
+    }
     ShareErrorCode randbit_parties(hbmpc_ctx* c, const void* a, const void* ta, const void* tb, const void* tc, size_t N, size_t n, size_t t, void* desh,
                                    void* Y, void* Z, void* deop, void* sq, void* sqop, void* out, uint8_t* st, uint8_t* rde, uint8_t* rsq,
                                    hbmpc_recover_summary* s1, hbmpc_recover_summary* s2, hbmpc_recover_summary* s3, hbmpc_recover_summary* s4,

@@ -2,7 +2,7 @@
 //
 // hbmpc_[gl_]dev_triplegen_parties, hbmpc_dev_fpmul_parties, hbmpc_dev_truncpr_parties, hbmpc_[gl_]dev_mul_parties,
 // hbmpc_[gl_]dev_randbit_parties and hbmpc_[gl_]dev_input_parties each ask plan_protocol once; either form writes the same bytes
-// to every output buffer.
+// to every output buffer.  hbmpc_[gl_]dev_batchrecon_parties asks plan_batchrecon, below, the same way.
 // Two declines stay with the executor because they depend on a launcher or on the decode, not on the call's shape:
 //   - the launchers' dry run (launch_*_wave(.., true): the LDS size and the LDS attribute): the call then runs its separate launches;
 //   - the HBMPC_NOT_FUSED answer of batch_recover_dev to the pair form: the open then writes the shares and decodes them.
@@ -65,6 +65,27 @@ inline ProtocolPlan plan_protocol(const ProtocolKnobs& k, const ProtocolShape& s
     }
     // the pair form: ahead from ~8 000 elements (tools/sweep_fused_fpmul.py); Goldilocks has none
     return ProtocolPlan{one, lane_share(s.t + 2, 32, s.t), lane_share(s.t + 1, 64, s.t), (fpmul || mul) && !gold && s.N >= k.pair_decode_min};
+}
+
+// ---- hbmpc_[gl_]dev_batchrecon_parties --------------------------------------------------------------------------------------------
+// BatchRecon has a degree and two sender sets, which ProtocolShape has no place for, and its threshold is a context's own: a shape, a
+// plan and a function of its own, so that ProtocolKnobs, ProtocolCall and every answer of plan_protocol stay as they are.
+// the call: N elements per party in chunks of d + 1, n parties, t faults, S1 EvalBatch senders, S2 RevealBatch senders
+struct BatchReconShape {
+    size_t N, n, t, d, S1, S2;
+};
+struct BatchReconPlan {
+    bool one_launch;  // a workgroup per chunk (kernels_batchrecon_wg.hpp) instead of the three launches
+    int lk_eval;      // the EvalBatch arm: 1 << lk_eval adjacent lanes share the products of a (recipient, row)
+};
+// fused_batchrecon_max: hbmpc_set_fused_batchrecon, in chunks (0: never one launch)
+inline BatchReconPlan plan_batchrecon(const ProtocolKnobs& k, size_t fused_batchrecon_max, const BatchReconShape& s) {
+    // one launch has no OEC round and writes a failed chunk itself, so both arms decode from exactly d + t + 1 senders (a failed chunk is
+    // final: what the separate decodes then do in one launch each); the (party, recipient) pairs fit the workgroup
+    const bool one = !k.force_generic && k.direct_fail && (k.impl == IMPL_U29 || k.impl == IMPL_GOLD) && s.n <= 16 && s.S1 == s.d + s.t + 1 &&
+                     s.S2 == s.S1 && s.N / (s.d + 1) <= fused_batchrecon_max;
+    // lane pairs over U29 while the n (t + 1) rows fit half the workgroup (n = 16, t = 5: 192 lanes); n (t + 1) <= 256 for every covered shape
+    return BatchReconPlan{one, k.impl == IMPL_U29 && 2 * s.n * (s.t + 1) <= 256 ? 1 : 0};
 }
 
 }  // namespace hbmpc

@@ -78,6 +78,7 @@ FUSED_TRUNCPR_DEFAULT = 768  # hbmpc_set_fused_truncpr's default (csrc/hbmpc_cap
 FUSED_MUL_DEFAULT = 1024  # hbmpc_set_fused_mul's default (csrc/hbmpc_capi.hip)
 FUSED_INPUT_DEFAULT = 768  # hbmpc_set_fused_input's default (csrc/hbmpc_capi.hip)
 FUSED_RANDBIT_DEFAULT = {"fr": 256, "goldilocks": 1024}  # hbmpc_set_fused_randbit's default per field (FUSED_RANDBIT_FR / _GL, csrc/hbmpc_capi.hip)
+FUSED_BATCHRECON_DEFAULT = {"fr": 512, "goldilocks": 256}  # hbmpc_set_fused_batchrecon's default per field (FUSED_BATCHRECON_FR / _GL, csrc/hbmpc_capi.hip)
 FUSED_PRANDBIT_DEFAULT = 256  # hbmpc_set_fused_prandbit's default (FUSED_PRANDBIT, csrc/hbmpc_capi.hip)
 
 
@@ -626,6 +627,23 @@ class Engine:
     def set_fused_input(self, max_elements: int):
         """hbmpc_dev_input_parties is one launch up to this many batch elements (0: always two)"""
         assert self.L.hbmpc_set_fused_input(self.ctx, C.c_size_t(max_elements)) == 0
+
+    def batchrecon_parties(self, eval_senders, reveal_senders, x_d, N, n, d, t, y_d, z_d, opened_d, rstatus_d=0, status_d=0, summary_first_d=0,
+                           summary_d=0, stream=0):
+        """BatchRecon for all n parties of this device in one call (hbmpc_[gl_]dev_batchrecon_parties; the sender lists are party ids in
+        any order): every party's encode of its chunks of d + 1, the recipients' P(0) decodes from eval_senders, the coefficient decode
+        of the revealed values from reveal_senders.  One launch for a small batch with exactly d + t + 1 senders in both sets and
+        n <= 16, three otherwise; returns the ShareErrorCode"""
+        ids1 = (C.c_size_t * max(len(eval_senders), 1))(*eval_senders)
+        ids2 = (C.c_size_t * max(len(reveal_senders), 1))(*reveal_senders)
+        return self._f("dev_batchrecon_parties")(self.ctx, ids1, C.c_size_t(len(eval_senders)), ids2, C.c_size_t(len(reveal_senders)),
+                                                 C.c_void_p(x_d), C.c_size_t(N), C.c_size_t(n), C.c_size_t(d), C.c_size_t(t),
+                                                 *(C.c_void_p(p) for p in (y_d, z_d, opened_d, rstatus_d, status_d, summary_first_d, summary_d)),
+                                                 C.c_void_p(stream))
+
+    def set_fused_batchrecon(self, max_chunks: int):
+        """hbmpc_[gl_]dev_batchrecon_parties is one launch up to this many chunks of d + 1 elements (0: always three)"""
+        assert self.L.hbmpc_set_fused_batchrecon(self.ctx, C.c_size_t(max_chunks)) == 0
 
     def dev_beaver_open_shares_paired(self, a_d, b_d, x_d, y_d, N, parties, de_d, stream=0):
         """de[party][0][N] = a - x, de[party][1][N] = b - y: one P(0) decode over 2 N values per sender opens both"""

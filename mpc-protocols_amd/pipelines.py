@@ -217,6 +217,49 @@ class Output(_Pipe):
         return self.download_named(which, (self.n, self.N) if which == "sh" else (self.N,))
 
 
+class BatchRecon(_Pipe):
+    """BatchRecon (honeybadger/batch_recon/batch_recon.rs) of N = G (d + 1) shared values of degree d for n parties, in either field.
+    Buffers: x [party][N] (input); Y [party][recipient][G] the EvalBatch messages; Z [recipient][G] the RevealBatch messages; opened [N];
+    rstatus n G bytes (byte j G + g: recipient j's decode of chunk g), status G bytes; summary_first / summary the two decodes'.
+    eval_senders / reveal_senders: parties 0 .. S - 1 whose messages everyone decodes from (0: d + t + 1, a decode with no OEC round).
+    run() is one library call (hbmpc_[gl_]dev_batchrecon_parties): ONE launch up to hbmpc_set_fused_batchrecon chunks (512 over Fr, 256 over Goldilocks) when both
+    sets have exactly d + t + 1 senders and n <= 16, three launches otherwise.  deal() / finish() are its two arms as separate launches (the
+    encode and the recipients' decodes up to Z; the decode of Z): rows of Z may be rewritten in between."""
+
+    def __init__(self, eng, n, t, d, N, eval_senders=0, reveal_senders=0, stream=None):
+        self.n, self.t, self.d, self.N, self.G = n, t, d, N, N // (d + 1) if d + 1 else 0
+        super().__init__(eng, self._create(eng, "hbmpc_pipe_batchrecon_create", n, t, d, N, eval_senders, reveal_senders, stream=stream or 0), stream or 0)
+
+    def upload(self, x):
+        self.upload_named("x", x)
+
+    def deal(self, check=False):
+        self._call("hbmpc_pipe_deal", check)
+
+    def finish(self, check=False):
+        self._call("hbmpc_pipe_finish", check)
+
+    def download(self, which="opened"):
+        shape = {"x": (self.n, self.N), "Y": (self.n, self.n, self.G), "Z": (self.n, self.G), "opened": (self.N,)}[which]
+        return self.download_named(which, shape)
+
+    def bytes_of(self, name, nbytes):
+        """raw bytes of a named buffer (status bytes, summaries): hbmpc_pipe_download counts field elements"""
+        out = np.zeros(nbytes, dtype=np.uint8)
+        self.sync()
+        self._rc(self.eng.L.hbmpc_memcpy_d2h(self.eng.ctx, out.ctypes.data_as(C.c_void_p), C.c_void_p(self.buffer(name)[0]),
+                                             C.c_size_t(nbytes), C.c_void_p(self.stream)), f"bytes of {name!r}")
+        self.sync()
+        return out
+
+    def status(self, which="status"):
+        """the status bytes: "status" [G] of the revealed values' decode, "rstatus" [n][G] of the recipients' decodes"""
+        return self.bytes_of("rstatus", self.n * self.G).reshape(self.n, self.G) if which == "rstatus" else self.bytes_of("status", self.G)
+
+    def summary_first(self):
+        return self.bytes_of("summary_first", 16).view(np.uint32)
+
+
 class TruncPr(_Pipe):
     """TruncPr (fpmul/truncpr.rs:185-318) of N values for n parties: k-bit values, m fractional bits dropped.  Buffers a, rint, rdash,
     osh, out are [party][N], rbits [party][m][N], cop [N] the opened value, status [N] bytes, summary the open's.  open_senders as in

@@ -333,6 +333,13 @@ impl GpuShares {
         let rc = unsafe { sys::hbmpc_pipe_output_create(self.ctx, n, t, values, 0, stream, &mut p) };
         self.wrap(rc, p, n)
     }
+    /// `BatchReconNode` for all n parties (honeybadger/batch_recon/batch_recon.rs:144-185, 371-391, 451-467): buffer x ([party][values],
+    /// values a multiple of degree + 1), Y, Z the two arms' messages, opened ([values]); both arms decode from parties 0 .. degree + t
+    pub fn pipe_batchrecon(&self, n: usize, t: usize, degree: usize, values: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_batchrecon_create(self.ctx, n, t, degree, values, 0, 0, stream, &mut p) };
+        self.wrap(rc, p, n)
+    }
     /// `TruncPrNode` on its own for all n parties (fpmul/truncpr.rs:185-318): buffers a, rint ([party][values]), rbits ([party][m][values])
     pub fn pipe_truncpr(&self, n: usize, t: usize, values: usize, k: usize, m: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
         let mut p = std::ptr::null_mut();
