@@ -693,6 +693,66 @@ ShareErrorCode hbmpc_gl_dev_batchrecon_parties(hbmpc_ctx* ctx, const size_t* eva
                                                const uint64_t* x, size_t N, size_t n, size_t d, size_t t, uint64_t* y_ws, uint64_t* z_out,
                                                uint64_t* opened_out, uint8_t* rstatus_out, uint8_t* status_out,
                                                hbmpc_recover_summary* summary_first_dev, hbmpc_recover_summary* summary_dev, void* stream);
+/* RanShaNode (share_gen/share_gen.rs:232-289, 401-454, 516-530, 199-203) for a device that holds every party: K columns per dealer,
+ * degree t -> (n - 2t) K random sharings per party, verified by parties 0 .. 2t - 1 from the shares of parties 0 .. verify_senders - 1.
+ * A layer below hbmpc_pipe_ransha_create, for a caller with buffers of its own.
+ *   coeffs   [dealer][K][t + 1]       the dealers' polynomials, column 0 the secret (hbmpc_dev_fill_coeffs or the host); or NULL:
+ *   dealt    [dealer][recipient][K]   with coeffs the ShareMessages, an OUTPUT; with coeffs == NULL the INPUT, the shares as received
+ *                                     (a Byzantine dealer's shares need lie on no polynomial)
+ *   out      [party][K][n - 2t]       rows 2t .. n - 1 of y[i][j, k] = sum_p alpha_i^p dealt[p][j, k], the reference's order (:199-203)
+ *   yv_out   [party][verifier][K]     rows 0 .. 2t - 1: what party j sends verifier i (may be null when t == 0)
+ *   ws_dev   2 n n K + max(2t, t + 1) K elements of workspace; its contents are unspecified (one launch does not touch it)
+ *   status_out [2t K]                 byte i K + k: verifier i's decode of column k;  summary_dev: that decode's (either may be null)
+ *   bad_dev  [2]                      WRITTEN, not accumulated: the failing (verifier, column) pairs and the lowest failing column
+ * Every buffer, status byte and the summary hold exactly what these calls leave, in this order: hbmpc_dev_vandermonde_apply_parties
+ * (coeffs, K, n, t, n parties -> dealt; only with coeffs), hbmpc_dev_vandermonde_apply_rows_split (dealt, row stride and G = n K, n,
+ * d = n - 1, list rows 2t .. n - 1 as one slice {out, (n - 2t) K, 0, K}, the others to yv_out; t == 0: _rows_lists), bad_dev =
+ * {0, 0xffffffff}, hbmpc_dev_recover_check_degree_strided (senders 0 .. verify_senders - 1, yv_out, row stride 2t K, G = K, n, t,
+ * groups = 2t, group_stride = K).  These are the calls of the handle's "together" form.  With t == 0 there is no verifier: status_out
+ * and summary_dev are not written.  With n < 3t + 1 recover_secret refuses every column (robust_interpolate.rs:290): bad_dev =
+ * {2t K, 0}, every status byte InvalidInput, the summary {2t K, 2t K, 0, InvalidInput}.  With verify_senders > 2t + 1 the decode is a
+ * call per verifier into the same status bytes and summary: they hold the last verifier's (K bytes).
+ * InvalidInput, before the first launch (a refused call has written nothing): a null required buffer (coeffs == NULL selects the dealt
+ * shares as input, so dealt is required either way), K == 0, n <= 2t or n > 255, verify_senders < 2t + 1 or > n, and every size at which
+ * the together form's single calls do not exist -- K >= 2^19 or a dealt block (n n K elements) of 4 GiB or more; below both no deal is
+ * split into several calls, which the call checks all the same: the handles are the path there.  TypeMismatch: the Fr call on a Goldilocks context and the other way round.
+ * With verify_senders == 2t + 1, 1 <= t, 3t + 1 <= n <= 16, nothing forcing the generic or the OEC kernels (hbmpc_set_force_generic,
+ * hbmpc_set_single_launch_decode), the tables within a workgroup's LDS and at most hbmpc_set_fused_producers columns the call is ONE launch, a
+ * workgroup per column (csrc/kernels_producers_wg.hpp; a Sat32 context never takes it); otherwise the launches above.  Same bytes in
+ * either form.  Measured on an MI355X (ms per eager call at (16, 5) from the polynomials, one launch / separate launches / the handle's
+ * run(), profiles/fused_producers_sweep.txt): RanSha over Fr 0.016 / 0.029 / 0.026 at K = 1, 0.023 / 0.055 / 0.061 at 256, 0.113 / 0.060 /
+ * 0.059 at the node's 2 048; RanDouSha over Fr 0.029 / 0.053 / 0.049, 0.039 / 0.110 / 0.121, 0.144 / 0.117 / 0.115 at the node's 1 536: the
+ * default threshold is 256 columns over both fields, and the node's own sizes take the separate launches.
+ * Not here: dealing from a seed, sessions, RBC of the verdicts, the wire envelope, the OEC round for verify_senders > 2t + 1 in one
+ * launch. */
+ShareErrorCode hbmpc_dev_ransha_parties(hbmpc_ctx* ctx, const U256* coeffs, U256* dealt, size_t K, size_t n, size_t t, size_t verify_senders,
+                                        U256* out, U256* yv_out, U256* ws_dev, uint8_t* status_out, hbmpc_recover_summary* summary_dev,
+                                        uint32_t* bad_dev, void* stream);
+ShareErrorCode hbmpc_gl_dev_ransha_parties(hbmpc_ctx* ctx, const uint64_t* coeffs, uint64_t* dealt, size_t K, size_t n, size_t t,
+                                           size_t verify_senders, uint64_t* out, uint64_t* yv_out, uint64_t* ws_dev, uint8_t* status_out,
+                                           hbmpc_recover_summary* summary_dev, uint32_t* bad_dev, void* stream);
+/* DouShaNode + RanDouShaNode (double_share/double_share_generation.rs:151-215, ran_dou_sha/mod.rs:371-449, 569-602, 314-331) the same
+ * way: both sharings (degrees t and 2t) of K columns per dealer -> (t + 1) K double sharings per party, verified by parties
+ * t + 1 .. n - 1, each through ALL n shares.  Two of every buffer of the call above (both coefficient arrays or neither), with
+ *   out_t, out_2t   [party][K][t + 1]            rows 0 .. t (:314-331);   yv_t_out, yv_2t_out [party][n - t - 1][K]: rows t + 1 .. n - 1
+ *   ws_dev          2 n n K + (n - t - 1) n K elements of workspace, contents unspecified
+ *   sel_*_out, st_*_out, G = (n - t - 1) K entries, entry (verifier - t - 1) K + k: what the field's verifier calls leave --
+ *     Fr          sel [G][2] = (constant term, coefficient t resp. 2t), st [G] status bytes (hbmpc_dev_interpolate_degree_check_strided)
+ *     Goldilocks  sel [G] = the constant terms, st [G] uint32 = the degrees (hbmpc_gl_dev_batch_interpolate_c0)
+ *   bad_dev [2]     WRITTEN: the (verifier, column) pairs without "degree exactly t, degree exactly 2t, equal constant terms"
+ * Every buffer holds exactly what these calls leave, in this order: hbmpc_dev_vandermonde_apply_parties twice (only with coefficients),
+ * hbmpc_dev_vandermonde_apply_rows_split twice (list rows 0 .. t), bad_dev = {0, 0xffffffff}, then over Fr
+ * hbmpc_dev_interpolate_degree_check_strided twice (ids 0 .. n - 1, row stride G, K columns, groups = n - t - 1, group_stride = K) and
+ * hbmpc_dev_check_double_share_sel (G, columns = K); over Goldilocks hbmpc_gl_dev_batch_interpolate_c0 twice (row stride G, G columns) and
+ * hbmpc_dev_check_double_share_c0_columns (G, columns = K).  With n == 1 there is no verifier.
+ * Refusals as above (no verify_senders).  ONE launch under the same rule without the conditions on verify_senders and 3t + 1. */
+ShareErrorCode hbmpc_dev_randousha_parties(hbmpc_ctx* ctx, const U256* coeffs_t, const U256* coeffs_2t, U256* dealt_t, U256* dealt_2t, size_t K,
+                                           size_t n, size_t t, U256* out_t, U256* out_2t, U256* yv_t_out, U256* yv_2t_out, U256* ws_dev,
+                                           U256* sel_t_out, U256* sel_2t_out, void* st_t_out, void* st_2t_out, uint32_t* bad_dev, void* stream);
+ShareErrorCode hbmpc_gl_dev_randousha_parties(hbmpc_ctx* ctx, const uint64_t* coeffs_t, const uint64_t* coeffs_2t, uint64_t* dealt_t,
+                                              uint64_t* dealt_2t, size_t K, size_t n, size_t t, uint64_t* out_t, uint64_t* out_2t,
+                                              uint64_t* yv_t_out, uint64_t* yv_2t_out, uint64_t* ws_dev, uint64_t* sel_t_out,
+                                              uint64_t* sel_2t_out, void* st_t_out, void* st_2t_out, uint32_t* bad_dev, void* stream);
 /* Output's client side for a device that holds every party's result shares (honeybadger/output/output.rs:157-177):
  * recover_secret(.., n, t) per element.  sh is [party][N], sender_ids[S] PARTY ids, out [N]; out, status_out[N] and summary_dev (either
  * may be null) hold exactly what hbmpc_dev_batch_recover_p0 leaves for G = N, d = t from the senders' rows, which are read in place
@@ -1166,6 +1226,9 @@ ShareErrorCode hbmpc_set_fused_input(hbmpc_ctx* ctx, size_t max_elements);
 /* hbmpc_[gl_]dev_batchrecon_parties runs as one launch up to max_chunks chunks of d + 1 elements (default 512 over Fr, 256 over
  * Goldilocks; 0: always the three separate launches).  Same bytes either way (A/B aid). */
 ShareErrorCode hbmpc_set_fused_batchrecon(hbmpc_ctx* ctx, size_t max_chunks);
+/* hbmpc_[gl_]dev_ransha_parties and hbmpc_[gl_]dev_randousha_parties run as one launch up to max_columns columns per dealer (default
+ * 256 over Fr, 256 over Goldilocks; 0: always the separate launches).  Same bytes either way (A/B aid). */
+ShareErrorCode hbmpc_set_fused_producers(hbmpc_ctx* ctx, size_t max_columns);
 /* hbmpc_[gl_]dev_randbit_parties runs as one launch up to max_chunks chunks of t + 1 elements (default 256 over Fr, 1024 over
  * Goldilocks; 0: always the nine separate launches).  Same bytes either way (A/B aid). */
 ShareErrorCode hbmpc_set_fused_randbit(hbmpc_ctx* ctx, size_t max_chunks);

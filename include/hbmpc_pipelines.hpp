@@ -315,6 +315,50 @@ class RanDouSha : public Producer {
     }
 };
 
+// The producers as ONE device call each for a caller with buffers of its own (hbmpc_dev_ransha_parties / hbmpc_dev_randousha_parties: one
+// launch for a small batch, the handles' together form otherwise), over Fr.  The two functions own what the caller does not keep: what the
+// parties send the verifiers, the verifiers' results and the workspace live in a DevBlock for the call and are freed after the
+// stream has been waited for; verdict_out = {failing (verifier, column) pairs, lowest failing column}.
+class DevBlock {
+  public:
+    DevBlock(hbmpc_ctx* ctx, size_t bytes) : ctx_(ctx) { pl_check(hbmpc_dev_alloc(ctx, bytes ? bytes : 16, &p_), ctx, "hbmpc_dev_alloc"); }
+    DevBlock(const DevBlock&) = delete;
+    DevBlock& operator=(const DevBlock&) = delete;
+    ~DevBlock() { hbmpc_dev_free(ctx_, p_); }
+    template <class T>
+    T* at(size_t byte_offset) const { return reinterpret_cast<T*>(static_cast<unsigned char*>(p_) + byte_offset); }
+
+  private:
+    hbmpc_ctx* ctx_;
+    void* p_ = nullptr;
+};
+// coeffs [dealer][K][t + 1] (or null: dealt is the input) -> dealt [dealer][recipient][K], out [party][K][n - 2t]
+inline void ransha_parties(hbmpc_ctx* ctx, const U256* coeffs, U256* dealt, size_t K, size_t n, size_t t, U256* out, uint32_t verdict_out[2],
+                           void* stream, size_t verify_senders = 0) {
+    const size_t eb = sizeof(U256), yv = n * 2 * t * K * eb, ws = (2 * n * n + (2 * t > t + 1 ? 2 * t : t + 1)) * K * eb;
+    DevBlock blk(ctx, yv + ws + 16);
+    uint32_t* bad = blk.at<uint32_t>(yv + ws);
+    pl_check(hbmpc_dev_ransha_parties(ctx, coeffs, dealt, K, n, t, verify_senders ? verify_senders : 2 * t + 1, out, blk.at<U256>(0), blk.at<U256>(yv), nullptr,
+                                      nullptr, bad, stream),
+             ctx, "hbmpc_dev_ransha_parties");
+    pl_check(hbmpc_memcpy_d2h(ctx, verdict_out, bad, 8, stream), ctx, "d2h");
+    pl_check(hbmpc_stream_sync(ctx, stream), ctx, "sync");
+}
+// both coefficient arrays (or both null) -> dealt_t, dealt_2t, out_t, out_2t [party][K][t + 1]
+inline void randousha_parties(hbmpc_ctx* ctx, const U256* coeffs_t, const U256* coeffs_2t, U256* dealt_t, U256* dealt_2t, size_t K, size_t n, size_t t,
+                              U256* out_t, U256* out_2t, uint32_t verdict_out[2], void* stream) {
+    const size_t eb = sizeof(U256), nver = n - t - 1, G = nver * K, yv = n * G * eb, sel = 2 * G * eb, st = (G + 15) / 16 * 16;
+    const size_t ws = (2 * n * n + nver * n) * K * eb;
+    DevBlock blk(ctx, 2 * yv + 2 * sel + ws + 2 * st + 16);
+    uint32_t* bad = blk.at<uint32_t>(2 * yv + 2 * sel + ws + 2 * st);
+    pl_check(hbmpc_dev_randousha_parties(ctx, coeffs_t, coeffs_2t, dealt_t, dealt_2t, K, n, t, out_t, out_2t, blk.at<U256>(0), blk.at<U256>(yv),
+                                         blk.at<U256>(2 * yv + 2 * sel), blk.at<U256>(2 * yv), blk.at<U256>(2 * yv + sel), blk.at<void>(2 * yv + 2 * sel + ws),
+                                         blk.at<void>(2 * yv + 2 * sel + ws + st), bad, stream),
+             ctx, "hbmpc_dev_randousha_parties");
+    pl_check(hbmpc_memcpy_d2h(ctx, verdict_out, bad, 8, stream), ctx, "d2h");
+    pl_check(hbmpc_stream_sync(ctx, stream), ctx, "sync");
+}
+
 // RandBit of N shared values for n parties (N a multiple of t + 1): Beaver square of a, BatchRecon of a^2, phase 2
 // (fpmul/rand_bit.rs:242-293,197-220).  Buffers a, ta, tb, tc (inputs), out (output), sq: [party][N]; sqop: [N].  Elements are
 // those of the context's field (U256, or 8-byte Goldilocks values: cast the pointers).  run(true) fails with HBMPC_ZERO_SQUARE /

@@ -25,6 +25,7 @@
 #include "kernels_triplegen_wg.hpp"
 #include "kernels_randbit_wg.hpp"
 #include "kernels_batchrecon_wg.hpp"
+#include "kernels_producers_wg.hpp"
 #include "kernels_prandbit_wg.hpp"
 #include "bfly_ring_plan.hpp"
 #include "launchers.hpp"
@@ -36,6 +37,7 @@
 #include "encode_route.hpp"
 #include "recover_route.hpp"
 #include "protocol_route.hpp"
+#include "producer_route.hpp"
 #include "prandbit_route.hpp"
 #include "tables_sqrt.hpp"
 #include "tables_riss.hpp"
@@ -54,6 +56,10 @@ constexpr size_t FUSED_PRANDBIT = 256;
 // the largest swept count at which one launch was not slower than the three launches at (4, 1, d = 1), (16, 5, d = 5) and
 // (16, 5, d = 10), eager and replayed (profiles/fused_batchrecon_sweep.txt)
 constexpr size_t FUSED_BATCHRECON_FR = 512, FUSED_BATCHRECON_GL = 256;
+// hbmpc_[gl_]dev_ransha_parties / _randousha_parties as one launch: the defaults of hbmpc_set_fused_producers per field, in columns per
+// dealer -- the largest swept count at which one launch was not slower than the separate launches at (4, 1), (7, 2) and (16, 5), both
+// producers, both input modes, eager and replayed (profiles/fused_producers_sweep.txt)
+constexpr size_t FUSED_PRODUCERS_FR = 256, FUSED_PRODUCERS_GL = 256;
 constexpr size_t STAGE_PIN_BLOCK = (size_t)2048 << 10;  // pinned host block of the small-call staging path (Stage, hbmpc_scrub_staging)
 struct hbmpc_ctx {
     int device = 0;
@@ -96,6 +102,7 @@ struct hbmpc_ctx {
     size_t fused_input_max = 768;                  // hbmpc_dev_input_parties: the same (profiles/fused_input_sweep.txt)
     size_t fused_randbit_max = FUSED_RANDBIT_FR;   // hbmpc_dev_randbit_parties: one launch (a workgroup per chunk of t + 1 elements) up to this many chunks (0: never); per field, hbmpc_create
     size_t fused_batchrecon_max = FUSED_BATCHRECON_FR;  // hbmpc_dev_batchrecon_parties: one launch (a workgroup per chunk of d + 1 elements) up to this many chunks (0: never); per field, hbmpc_create
+    size_t fused_producers_max = FUSED_PRODUCERS_FR;    // hbmpc_dev_ransha_parties / _randousha_parties: one launch (a workgroup per column) up to this many columns per dealer (0: never); per field, hbmpc_create
     size_t fused_prandbit_max = FUSED_PRANDBIT;    // hbmpc_dev_prandbit_parties / _prandint_parties (read from the Fr context): the same, in chunks of t + 1 elements
     bool gather_row_copies = false;                // hbmpc_dev_gather_party_major: take the per-row peer copies even where the 2-D copy applies (A/B aid)
     bool list_rows_in_kernel = true;               // the producers' mixing step writes the parties' lists itself (k_mfma_bfly<.., LISTS>)
@@ -392,7 +399,7 @@ extern "C" ShareErrorCode hbmpc_create(int device, FieldKind field_kind, hbmpc_c
     }
     const char* env = getenv("HBMPC_FIELD_IMPL");
     if (env && std::string(env) == "sat32") ctx->impl = IMPL_SAT32;
-    if (field_kind == Goldilocks64) ctx->impl = IMPL_GOLD, ctx->fused_randbit_max = FUSED_RANDBIT_GL, ctx->fused_batchrecon_max = FUSED_BATCHRECON_GL;
+    if (field_kind == Goldilocks64) ctx->impl = IMPL_GOLD, ctx->fused_randbit_max = FUSED_RANDBIT_GL, ctx->fused_batchrecon_max = FUSED_BATCHRECON_GL, ctx->fused_producers_max = FUSED_PRODUCERS_GL;
     env = getenv("HBMPC_MATRIX_CORES");
     if (env && std::string(env) == "0") ctx->matrix_cores = false;
     hipDeviceProp_t prop;
@@ -468,6 +475,7 @@ KNOB_SETTER(hbmpc_set_fused_mul, fused_mul_max)
 KNOB_SETTER(hbmpc_set_fused_input, fused_input_max)
 KNOB_SETTER(hbmpc_set_fused_randbit, fused_randbit_max)
 KNOB_SETTER(hbmpc_set_fused_batchrecon, fused_batchrecon_max)
+KNOB_SETTER(hbmpc_set_fused_producers, fused_producers_max)
 KNOB_SETTER(hbmpc_set_fused_prandbit, fused_prandbit_max)
 KNOB_SETTER(hbmpc_set_fpmul_pair_decode, pair_decode_min)
 #undef KNOB_SETTER
@@ -2305,3 +2313,4 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
 #include "capi_batchrecon.inc"
 #include "capi_randbit.inc"
 #include "capi_prandbit.inc"
+#include "capi_producers.inc"

@@ -124,6 +124,9 @@ void launch_randbit_wg(int impl, const RandBitWgArgs& a, hipStream_t s);  // Ran
 // field, the layout does not fit a workgroup's LDS or the LDS attribute could not be set; dry_run: only say which
 struct BatchReconWgArgs;
 bool launch_batchrecon_wg(int impl, const BatchReconWgArgs& a, int device, hipStream_t s, bool dry_run);
+// RanSha / RanDouSha (randousha), a workgroup per batch element (kernels_producers_wg.hpp): U29 or Goldilocks.  false as above
+struct ProducersWgArgs;
+bool launch_producers_wg(int impl, bool randousha, const ProducersWgArgs& a, int device, hipStream_t s, bool dry_run);
 bool launch_fpmul_wave(const FpmulWaveArgs& a, int device, hipStream_t s, bool dry_run);
 // TruncPrNode / FPDivConstNode (a.w set) the same way (kernels_truncpr_wave.hpp); dry_run: only say whether the LDS layout fits
 struct TruncprWaveArgs;

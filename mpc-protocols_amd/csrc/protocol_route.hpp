@@ -2,7 +2,8 @@
 //
 // hbmpc_[gl_]dev_triplegen_parties, hbmpc_dev_fpmul_parties, hbmpc_dev_truncpr_parties, hbmpc_[gl_]dev_mul_parties,
 // hbmpc_[gl_]dev_randbit_parties and hbmpc_[gl_]dev_input_parties each ask plan_protocol once; either form writes the same bytes
-// to every output buffer.  hbmpc_[gl_]dev_batchrecon_parties asks plan_batchrecon, below, the same way.
+// to every output buffer.  hbmpc_[gl_]dev_batchrecon_parties asks plan_batchrecon, below, the same way,
+// hbmpc_[gl_]dev_ransha_parties and hbmpc_[gl_]dev_randousha_parties plan_producers.
 // Two declines stay with the executor because they depend on a launcher or on the decode, not on the call's shape:
 //   - the launchers' dry run (launch_*_wave(.., true): the LDS size and the LDS attribute): the call then runs its separate launches;
 //   - the HBMPC_NOT_FUSED answer of batch_recover_dev to the pair form: the open then writes the shares and decodes them.
@@ -86,6 +87,42 @@ inline BatchReconPlan plan_batchrecon(const ProtocolKnobs& k, size_t fused_batch
                      s.S2 == s.S1 && s.N / (s.d + 1) <= fused_batchrecon_max;
     // lane pairs over U29 while the n (t + 1) rows fit half the workgroup (n = 16, t = 5: 192 lanes); n (t + 1) <= 256 for every covered shape
     return BatchReconPlan{one, k.impl == IMPL_U29 && 2 * s.n * (s.t + 1) <= 256 ? 1 : 0};
+}
+
+// ---- hbmpc_[gl_]dev_ransha_parties, hbmpc_[gl_]dev_randousha_parties ---------------------------------------------------------------
+// The producers have K columns per dealer instead of N elements, RanSha a verifier sender count, and their threshold is a context's own:
+// a shape, a plan and a function of their own, as for BatchRecon.
+enum class ProducerCall { RanSha, RanDouSha };
+// the call: K columns per dealer, n parties, t faults, S verify senders (RanSha; RanDouSha's verifiers read all n)
+struct ProducersShape {
+    ProducerCall call;
+    size_t K, n, t, S;
+};
+struct ProducersPlan {
+    bool one_launch;  // a workgroup per column (kernels_producers_wg.hpp) instead of the separate launches
+};
+// the LDS of a workgroup of the one-launch form (ProducersWgLds, kernels_producers_wg.hpp: elements 12 words apart and constants of 9
+// over U29, 2 and 2 over Goldilocks): per sharing the dealt and the mixed block and the verifiers' table, the Vandermonde table, the kept
+// coefficients and flags
+inline size_t producers_lds_bytes(bool gold, const ProducersShape& s) {
+    const size_t ls = gold ? 2 : 12, nl = gold ? 2 : 9, n = s.n, t = s.t;
+    const bool dou = s.call == ProducerCall::RanDouSha;
+    const size_t nver = dou ? n - t - 1 : 2 * t;
+    // the tables' constants: RanSha (2t + 1)(t + 1); RanDouSha over Fr n (t + 1) + n (2t + 1), over Goldilocks n n for each sharing
+    const size_t tabs = !dou ? (2 * t + 1) * (t + 1) : gold ? 2 * n * n : n * (3 * t + 2);
+    const size_t words = (dou ? 4 : 2) * n * n * ls + n * n * nl + tabs * nl + 4 * nver * ls + 64;
+    return (words + 16) * 4;  // every block starts on a multiple of 4 words
+}
+// fused_producers_max: hbmpc_set_fused_producers, in columns (0: never one launch)
+inline ProducersPlan plan_producers(const ProtocolKnobs& k, size_t fused_producers_max, const ProducersShape& s) {
+    // one launch has no OEC round and writes a failed column itself: RanSha's verifiers decode from exactly 2t + 1 senders, and below
+    // n = 3t + 1 recover_secret refuses every column, which the separate launches report.  t = 0 has no verifier's table to speak of (RanSha has
+    // no verifier at all) and stays with the separate launches.  The (row, party) pairs fit the workgroup: n <= 16.
+    const bool field = k.impl == IMPL_U29 || k.impl == IMPL_GOLD;
+    const bool shape = s.n <= 16 && s.t >= 1 && s.n > 2 * s.t && (s.call == ProducerCall::RanDouSha || (s.S == 2 * s.t + 1 && s.n >= 3 * s.t + 1));
+    const bool one = !k.force_generic && k.direct_fail && field && shape && producers_lds_bytes(k.impl == IMPL_GOLD, s) <= 160 * 1024 &&
+                     s.K <= fused_producers_max;
+    return ProducersPlan{one};
 }
 
 }  // namespace hbmpc

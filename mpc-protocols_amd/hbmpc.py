@@ -79,6 +79,7 @@ FUSED_MUL_DEFAULT = 1024  # hbmpc_set_fused_mul's default (csrc/hbmpc_capi.hip)
 FUSED_INPUT_DEFAULT = 768  # hbmpc_set_fused_input's default (csrc/hbmpc_capi.hip)
 FUSED_RANDBIT_DEFAULT = {"fr": 256, "goldilocks": 1024}  # hbmpc_set_fused_randbit's default per field (FUSED_RANDBIT_FR / _GL, csrc/hbmpc_capi.hip)
 FUSED_BATCHRECON_DEFAULT = {"fr": 512, "goldilocks": 256}  # hbmpc_set_fused_batchrecon's default per field (FUSED_BATCHRECON_FR / _GL, csrc/hbmpc_capi.hip)
+FUSED_PRODUCERS_DEFAULT = {"fr": 256, "goldilocks": 256}  # hbmpc_set_fused_producers's default per field (FUSED_PRODUCERS_FR / _GL, csrc/hbmpc_capi.hip)
 FUSED_PRANDBIT_DEFAULT = 256  # hbmpc_set_fused_prandbit's default (FUSED_PRANDBIT, csrc/hbmpc_capi.hip)
 
 
@@ -644,6 +645,30 @@ class Engine:
     def set_fused_batchrecon(self, max_chunks: int):
         """hbmpc_[gl_]dev_batchrecon_parties is one launch up to this many chunks of d + 1 elements (0: always three)"""
         assert self.L.hbmpc_set_fused_batchrecon(self.ctx, C.c_size_t(max_chunks)) == 0
+
+    def ransha_parties(self, coeffs_d, dealt_d, K, n, t, verify_senders, out_d, yv_d, ws_d, status_d=0, summary_d=0, bad_d=0, stream=0):
+        """RanSha for all n parties of this device in one call (hbmpc_[gl_]dev_ransha_parties): coeffs_d [dealer][K][t + 1] -> dealt_d
+        [dealer][recipient][K], or with coeffs_d = 0 dealt_d is the input; out_d [party][K][n - 2t], yv_d [party][verifier][K],
+        ws_d 2 n n K + max(2t, t + 1) K elements, bad_d [2] uint32 (written).  One launch for a small batch with exactly 2t + 1
+        verify senders and 3t + 1 <= n <= 16, the handle's together form otherwise; returns the ShareErrorCode"""
+        return self._f("dev_ransha_parties")(self.ctx, C.c_void_p(coeffs_d), C.c_void_p(dealt_d), C.c_size_t(K), C.c_size_t(n), C.c_size_t(t),
+                                             C.c_size_t(verify_senders),
+                                             *(C.c_void_p(p) for p in (out_d, yv_d, ws_d, status_d, summary_d, bad_d)), C.c_void_p(stream))
+
+    def randousha_parties(self, coeffs_t_d, coeffs_2t_d, dealt_t_d, dealt_2t_d, K, n, t, out_t_d, out_2t_d, yv_t_d, yv_2t_d, ws_d, sel_t_d,
+                          sel_2t_d, st_t_d, st_2t_d, bad_d, stream=0):
+        """DouSha + RanDouSha for all n parties of this device in one call (hbmpc_[gl_]dev_randousha_parties): two of every buffer of
+        ransha_parties, out_* [party][K][t + 1], yv_* [party][n - t - 1][K], ws_d 2 n n K + (n - t - 1) n K elements; sel_* / st_*:
+        what the field's verifier calls leave (Fr: (constant term, top coefficient) pairs and status bytes; Goldilocks: constant terms
+        and uint32 degrees).  One launch for a small batch with n <= 16; returns the ShareErrorCode"""
+        return self._f("dev_randousha_parties")(self.ctx, *(C.c_void_p(p) for p in (coeffs_t_d, coeffs_2t_d, dealt_t_d, dealt_2t_d)), C.c_size_t(K),
+                                                C.c_size_t(n), C.c_size_t(t),
+                                                *(C.c_void_p(p) for p in (out_t_d, out_2t_d, yv_t_d, yv_2t_d, ws_d, sel_t_d, sel_2t_d, st_t_d,
+                                                                          st_2t_d, bad_d)), C.c_void_p(stream))
+
+    def set_fused_producers(self, max_columns: int):
+        """hbmpc_[gl_]dev_ransha_parties / _randousha_parties are one launch up to this many columns per dealer (0: never)"""
+        assert self.L.hbmpc_set_fused_producers(self.ctx, C.c_size_t(max_columns)) == 0
 
     def dev_beaver_open_shares_paired(self, a_d, b_d, x_d, y_d, N, parties, de_d, stream=0):
         """de[party][0][N] = a - x, de[party][1][N] = b - y: one P(0) decode over 2 N values per sender opens both"""

@@ -410,6 +410,26 @@ impl<'a> GpuPipeline<'a> {
     fn name(name: &str) -> CString {
         CString::new(name).expect("buffer names have no NUL")
     }
+    /// `RanShaNode` for all n parties as ONE device call on the caller's own device buffers, no handle (hbmpc_dev_ransha_parties: one launch
+    /// for a small batch, the handle's together form otherwise): `coeffs` [dealer][K][t + 1] or null (then `dealt` [dealer][recipient][K]
+    /// is the input: `init_ransha_batch`'s received ShareMessages), `out` [party][K][n - 2t], `yv` [party][2t][K], `ws` 2 n n K +
+    /// max(2t, t + 1) K elements, `bad` [2] u32 (written).  Safety: every pointer is a device buffer of the size the header states
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn ransha_parties(gpu: &GpuShares, coeffs: *const sys::U256, dealt: *mut sys::U256, batch: usize, n: usize, t: usize, out: *mut sys::U256,
+                                 yv: *mut sys::U256, ws: *mut sys::U256, bad: *mut u32, stream: *mut core::ffi::c_void) -> Result<(), InterpolateError> {
+        let rc = sys::hbmpc_dev_ransha_parties(gpu.ctx, coeffs, dealt, batch, n, t, 2 * t + 1, out, yv, ws, std::ptr::null_mut(), std::ptr::null_mut(), bad, stream);
+        gpu.check(rc, n)
+    }
+    /// `DouShaNode` + `RanDouShaNode` the same way (hbmpc_dev_randousha_parties): two of every buffer, `out_*` [party][K][t + 1], `yv_*`
+    /// [party][n - t - 1][K], `ws` 2 n n K + (n - t - 1) n K elements, `sel_*` 2 (n - t - 1) K elements, `st_*` (n - t - 1) K bytes
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn randousha_parties(gpu: &GpuShares, coeffs: [*const sys::U256; 2], dealt: [*mut sys::U256; 2], batch: usize, n: usize, t: usize,
+                                    out: [*mut sys::U256; 2], yv: [*mut sys::U256; 2], ws: *mut sys::U256, sel: [*mut sys::U256; 2],
+                                    st: [*mut core::ffi::c_void; 2], bad: *mut u32, stream: *mut core::ffi::c_void) -> Result<(), InterpolateError> {
+        let rc = sys::hbmpc_dev_randousha_parties(gpu.ctx, coeffs[0], coeffs[1], dealt[0], dealt[1], batch, n, t, out[0], out[1], yv[0], yv[1], ws, sel[0], sel[1],
+                                                  st[0], st[1], bad, stream);
+        gpu.check(rc, n)
+    }
     /// a part of a preprocessing pipeline (`"ransha"`, `"randousha"`, `"triplegen"`): borrowed, lives as long as `self`
     pub fn part(&self, name: &str) -> Result<GpuPipeline<'a>, InterpolateError> {
         let mut p = std::ptr::null_mut();
