@@ -522,7 +522,18 @@ ShareErrorCode hbmpc_dev_check_double_share(hbmpc_ctx* ctx, const void* coeffs_t
 /* ==== a9/a11/a12/a13: element-wise share arithmetic of one party ============================
  * All arrays hold N elements of ONE party (same id, same degree: the id/degree checks of
  * common/mod.rs:167-300 are metadata and stay with the host mirror).  Host-pointer calls;
- * hbmpc_dev_* twins take device pointers + stream. */
+ * hbmpc_dev_* twins take device pointers + stream.
+ * The contract of every element-wise call of this header (these, the party-batched forms, hbmpc_[dev_]fr_op[_scalar],
+ * hbmpc_dev_beaver_open_shares_paired, hbmpc_dev_fpmul_middle and their hbmpc_gl_ twins):
+ *   - every operand is CANONICAL (below the modulus).  The kernels that only add or subtract work on the stored words
+ *     (raw_add_mod / raw_sub_mod, csrc/kernels_elem.hpp) with one conditional correction by r: they do NOT reduce a
+ *     non-canonical word, whose result is then wrong without any error (ADVICE.md's open finding).
+ *     hbmpc_dev_validate_canonical is the check for data that is not trusted.
+ *   - N = 0 is success and touches nothing, null buffers included.  With N > 0 a null input or output buffer is
+ *     InvalidInput ("null buffer") before anything is enqueued; r_bits alone may be null, and only when m = 0 (r' is then
+ *     all zeros).
+ *   - N beyond (2^31 - 1) * 256 elements (more workgroups of 256 lanes than one grid dimension holds) is InvalidInput;
+ *     parties outside 1..65535 is InvalidInput.  A call that is refused has written nothing. */
 /* triple_gen/triple_generation.rs:333-340: out = a*b - r2t */
 ShareErrorCode hbmpc_triple_local(hbmpc_ctx* ctx, const U256* a, const U256* b, const U256* r2t, size_t N, U256* out);
 /* triple_generation.rs:196-208: c = rt + opened */

@@ -1278,11 +1278,17 @@ extern "C" ShareErrorCode hbmpc_gl_make_vandermonde(hbmpc_ctx* ctx, size_t n, si
 
 // ---- element-wise ------------------------------------------------------------------------------
 // (the launchers of tu_elem.hip size the grid: a lane per element)
+// elem_grid (tu_elem.hip) takes the block count as a 32-bit grid dimension and HIP allows 2^31 - 1 of them: an N beyond that is refused
+// here, never launched on a wrapped grid
+static constexpr size_t ELEM_MAX_N = (size_t)0x7fffffff * 256;
 #define ELEM_PROLOGUE                                                           \
     if (!ctx) return InvalidInput;                                              \
     if (N == 0) return ShareSuccess;                                            \
+    if (N > ELEM_MAX_N) return fail(ctx, InvalidInput, "N out of range: more than 2^31 - 1 blocks of 256 elements"); \
     HIP_TRY(ctx, hipSetDevice(ctx->device));                                    \
     hipStream_t s = pick(ctx, stream);
+// every device buffer of a call with N > 0: a null one is refused before anything is enqueued
+#define ELEM_BUFS(...) do { for (const void* p_ : std::initializer_list<const void*>{__VA_ARGS__}) if (!p_) return fail(ctx, InvalidInput, "null buffer"); } while (0)
 
 #define CHECK_PARTIES(P) do { if ((P) == 0 || (P) > 65535) return fail(ctx, InvalidInput, "parties must be in 1..65535"); } while (0)
 
@@ -1292,6 +1298,7 @@ static uint32_t* as_words(void* p) { return (uint32_t*)p; }
 
 static ShareErrorCode fr_op_any(hbmpc_ctx* ctx, int op, const void* a, const void* b, size_t N, void* out, void* stream) {
     ELEM_PROLOGUE
+    ELEM_BUFS(a, b, out);
     if (op < 0 || op > 2) return fail(ctx, InvalidInput, "op must be 0 (add), 1 (sub) or 2 (mul)");
     const ElemConsts cs = elem_consts(ctx->impl);
     launch_binop(ctx->impl, op, as_words(a), as_words(b), N, cs, as_words(out), s);
@@ -1302,6 +1309,7 @@ static ShareErrorCode fr_op_any(hbmpc_ctx* ctx, int op, const void* a, const voi
 static ShareErrorCode fr_op_scalar_any(hbmpc_ctx* ctx, int op, const void* a, const void* scalar, size_t N, void* out, void* stream) {
     if (ctx && !scalar) return fail(ctx, InvalidInput, "null scalar");
     ELEM_PROLOGUE
+    ELEM_BUFS(a, out);
     if (op < 0 || op > 3) return fail(ctx, InvalidInput, "op must be 0 (a + s), 1 (a - s), 2 (a * s) or 3 (s - a)");
     ScalarArg sc;
     memset(&sc, 0, sizeof sc);
@@ -1323,6 +1331,7 @@ static ShareErrorCode fr_op_scalar_any(hbmpc_ctx* ctx, int op, const void* a, co
 static ShareErrorCode triple_local_any(hbmpc_ctx* ctx, const void* a, const void* b, const void* r2t, size_t N, void* out,
                                        void* stream) {
     ELEM_PROLOGUE
+    ELEM_BUFS(a, b, r2t, out);
     const ElemConsts cs = elem_consts(ctx->impl);
     launch_triple_local(ctx->impl, as_words(a), as_words(b), as_words(r2t), N, cs, as_words(out), s);
     HIP_TRY(ctx, hipGetLastError());
@@ -1396,6 +1405,7 @@ static ShareErrorCode triple_encode_any(hbmpc_ctx* ctx, const void* a, const voi
 static ShareErrorCode triple_finalize_any(hbmpc_ctx* ctx, const void* rt, const void* opened, size_t N, void* c_out,
                                           void* stream, size_t parties = 1) {
     ELEM_PROLOGUE
+    ELEM_BUFS(rt, opened, c_out);
     CHECK_PARTIES(parties);
     launch_triple_finalize(ctx->impl, as_words(rt), as_words(opened), N, (unsigned)parties, as_words(c_out), s);
     HIP_TRY(ctx, hipGetLastError());
@@ -1404,6 +1414,7 @@ static ShareErrorCode triple_finalize_any(hbmpc_ctx* ctx, const void* rt, const 
 static ShareErrorCode beaver_open_any(hbmpc_ctx* ctx, const void* a, const void* b, const void* x, const void* y, size_t N,
                                       void* d_sh, void* e_sh, void* stream) {
     ELEM_PROLOGUE
+    ELEM_BUFS(a, b, x, y, d_sh, e_sh);
     launch_beaver_open(ctx->impl, as_words(a), as_words(b), as_words(x), as_words(y), N, as_words(d_sh), as_words(e_sh), s);
     HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
@@ -1411,6 +1422,7 @@ static ShareErrorCode beaver_open_any(hbmpc_ctx* ctx, const void* a, const void*
 static ShareErrorCode beaver_open_pair_any(hbmpc_ctx* ctx, const void* a, const void* b, const void* x, const void* y, size_t N,
                                            size_t parties, void* de, void* stream) {
     ELEM_PROLOGUE
+    ELEM_BUFS(a, b, x, y, de);
     CHECK_PARTIES(parties);
     launch_beaver_open_pair(ctx->impl, as_words(a), as_words(b), as_words(x), as_words(y), N, (unsigned)parties, as_words(de), s);
     HIP_TRY(ctx, hipGetLastError());
@@ -1419,6 +1431,7 @@ static ShareErrorCode beaver_open_pair_any(hbmpc_ctx* ctx, const void* a, const 
 static ShareErrorCode beaver_finalize_any(hbmpc_ctx* ctx, const void* c, const void* x, const void* y, const void* d,
                                           const void* e, size_t N, void* z, void* stream, size_t parties = 1) {
     ELEM_PROLOGUE
+    ELEM_BUFS(c, x, y, d, e, z);
     CHECK_PARTIES(parties);
     const ElemConsts cs = elem_consts(ctx->impl);
     // the kernel loops over the parties (large N: the public operands are converted once per element) or spreads them
@@ -1596,6 +1609,8 @@ static ShareErrorCode truncpr_rdash_impl(hbmpc_ctx* ctx, const U256* r_bits, siz
                                          void* stream) {
     REQ_FR(ctx);
     ELEM_PROLOGUE
+    ELEM_BUFS(r_dash);
+    if (m && !r_bits) return fail(ctx, InvalidInput, "null buffer");  // m = 0: no bit shares are read, r' = 0
     CHECK_PARTIES(parties);
     if (!truncpr_params_ok(ctx, TP_M, 0, m)) return InvalidInput;
     const uint32_t* pow2;
@@ -1620,6 +1635,7 @@ extern "C" ShareErrorCode hbmpc_dev_truncpr_open_share(hbmpc_ctx* ctx, const U25
     REQ_FR(ctx);
     if (ctx && !truncpr_params_ok(ctx, TP_K, k, m)) return InvalidInput;
     ELEM_PROLOGUE
+    ELEM_BUFS(a, r_dash, r_int, open_out);
     const HFr two = HFr::from_u64(2);
     const HFr p2m = two.pow_u64(m), p2k = two.pow_u64(k - 1);
     const ElemConsts cs = elem_consts(ctx->impl, &p2m, &p2k);
@@ -1650,6 +1666,7 @@ static ShareErrorCode truncpr_finalize_impl(hbmpc_ctx* ctx, const U256* a, const
     REQ_FR(ctx);
     if (ctx && !truncpr_params_ok(ctx, TP_BYTES, 0, m)) return InvalidInput;
     ELEM_PROLOGUE
+    ELEM_BUFS(a, r_dash, c_open, d_out);
     CHECK_PARTIES(parties);
     const HFr inv = inv_pow2(ctx, m);
     const ElemConsts cs = elem_consts(ctx->impl, &inv);
