@@ -193,6 +193,7 @@ void hbmpc_graph_destroy(hbmpc_graph* graph);
  *   ransha         RanShaNode: deal, n x n Vandermonde, verifiers, output   share_gen/share_gen.rs:232-289,401-454,516-530,199-203
  *   randousha      DouShaNode deal + RanDouShaNode                           ran_dou_sha/mod.rs:371-449,569-602,314-331
  *   preprocessing  run_preprocessing's triple part: ransha -> a, b; randousha -> r; triplegen   honeybadger/mod.rs:1239-1393
+ *   fixedprep      run_preprocessing's steps 5 and 6: the PRandBit / PRandInt pools of mul_fixed   honeybadger/mod.rs:1396-1410,1951-2150
  * Sizes: N triples (a multiple of 2t+1) / N element pairs / K batch elements per dealer.  open_senders, verify_senders: how
  * many parties' shares an open / a RanSha verifier interpolates from; 0 = the reference's 2t + 1 (it acts as soon as that
  * many have arrived: multiplication.rs:388, truncpr.rs:202, share_gen.rs:497).  Every buffer of a pipeline lives in ONE device
@@ -206,6 +207,8 @@ void hbmpc_graph_destroy(hbmpc_graph* graph);
  *   ransha         coeffs ([dealer][K][t+1], column 0 the secret); S ([dealer][recipient][K]); y; out ([party][K][n-2t]); bad
  *   randousha      coeffs_t, coeffs_2t; S_t, S_2t; y_t, y_2t; out_t, out_2t ([party][K][t+1]); bad
  *   preprocessing  its parts by name (hbmpc_pipe_part: "ransha", "randousha", "triplegen"; borrowed handles)
+ *   fixedprep      its parts by name ("ransha", "randousha", "triplegen", "randbit", "prandbit", "prandint"); r_bits, r_bits2, r_int
+ *                  (see hbmpc_pipe_fixedprep_create)
  * run() only ENQUEUES on the handle's stream (checked mode, hbmpc_pipe_set_checked: it reads the summary back after every
  * decode and returns the failing chunk's error where the reference's `?` would).  deal() / finish() are the two halves of a
  * producer's run (tests corrupt the dealt shares in between).  capture() = two eager runs + a recorded one; replay() launches
@@ -285,6 +288,55 @@ ShareErrorCode hbmpc_pipe_randbit_create(hbmpc_ctx* ctx, size_t n, size_t t, siz
 ShareErrorCode hbmpc_pipe_prandbit_create(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl, size_t n, size_t t, size_t B, size_t lk_bits, size_t open_senders,
                                           void* stream, hbmpc_pipe** pipe_out);
 ShareErrorCode hbmpc_pipe_prandint_create(hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t B, size_t lk_bits, void* stream, hbmpc_pipe** pipe_out);
+/* FixedPrep: the second half of run_preprocessing (honeybadger/mod.rs:1396-1410, ensure_prandbit_shares :1951-2086 and
+ * ensure_prandint_shares :2088-2150) for all n parties -- ONE refill of empty r_bits / r_int pools, the ones mul_fixed drains
+ * (:1031-1045), from the dealers' Goldilocks polynomials and the RISS contributions.  The sizes are the reference's arithmetic:
+ *   R  = n_prandbit rounded up to a multiple of t + 1                              :1973-1974
+ *   T  = R rounded up to a multiple of 2t + 1                                      :1998-2001
+ *   K1 = ceil((R + 2 T) / (n - 2t))   RanSha's batch elements per dealer           :2004-2008, :1618-1619
+ *   K2 = ceil(T / (t + 1))            RanDouSha's                                  :1816-1817
+ * and every take is from the front (preprocessing.rs:126-163): RanSha's outputs [0, R) are RandBit's a, [R, R + T) the triples' a,
+ * [R + T, R + 2 T) the triples' b (:2012-2016, :1717-1726); the first T double sharings feed TripleGen; the first R triples feed
+ * RandBit (:2022-2026); RandBit's out is PRandBit's b_q with B = R; PRandInt runs with B = n_prandint.  The reference runs PRandBit /
+ * PRandInt in sessions of at most 64 (t + 1) elements; every element is independent, so one call gives their concatenation.
+ * Left-overs (T - R triples, the tails of the producers' lists) stay in the parts' buffers.
+ *   row of the pipeline table:  fixedprep   parts "ransha", "randousha", "triplegen", "randbit" (Goldilocks), "prandbit", "prandint"
+ *                                           (hbmpc_pipe_part; borrowed handles that keep all their buffers); buffers r_bits ([n][R] U256
+ *                                           = prandbit's b_p), r_bits2 ([n][R] bytes = its b_2), r_int ([n][n_prandint] U256 =
+ *                                           prandint's r_p)
+ * Inputs are the parts': coeffs (ransha), coeffs_t, coeffs_2t (randousha) -- uploaded, or filled by hbmpc_dev_fill_coeffs -- and contrib
+ * (prandbit, prandint).  One of n_prandbit / n_prandint may be 0: that half is absent (its parts and buffers are unknown names;
+ * :1966, :2098); both 0 is InvalidInput.
+ * create checks, in this order: ctx_fr, ctx_gl, pipe_out not null (InvalidInput); ctx_fr over Fr and ctx_gl over Goldilocks
+ * (TypeMismatch); both counts 0, n <= 2t (InvalidInput); then the parts' own creates in the order above, whose code it returns
+ * (shape, HBMPC_FIELD_CAPACITY, contexts on different devices).  *pipe_out is NULL after every refusal.  stream NULL: a stream of
+ * the handle's own, as for hbmpc_pipe_prandbit_create.
+ * run() is hbmpc_gl_dev_ransha_parties and hbmpc_gl_dev_randousha_parties from the polynomials, hbmpc_dev_take_rows of five slices
+ * (RandBit's a, TripleGen's a, b, rt, r2t), hbmpc_gl_dev_triplegen_parties, a take of three (RandBit's ta, tb, tc),
+ * hbmpc_gl_dev_randbit_parties, a take of one (b_q), hbmpc_dev_prandbit_parties, hbmpc_dev_prandint_parties -- the six existing device
+ * calls and one take per cut, nothing else; each call keeps its own one-launch rule and threshold.  deal() is both producers' encodes
+ * (the parts' deal()), finish() everything after, the producers' calls then reading the dealt shares S / S_t / S_2t; the same bytes as
+ * run().  The producers' calls write the parts' S, out and bad; their yv, workspace and verifier results are the handle's own and
+ * unspecified, and the parts' other buffers (x, y, yv, poly, status, summary, the verifiers' results) are not written.  Beyond the
+ * sizes those two calls accept (K1 >= 2^19 or a dealt block of 4 GiB) the producers run as the parts' own deal() / finish().
+ * (hbmpc_dev_vandermonde_apply_rows_lists writes at most two slices and RanSha's list has three consumers here, so the cut after the
+ * producers is always a take.)
+ * verdict() is both producers', combined as for preprocessing; summary() is PRandBit's.  Checked mode enqueues everything, synchronises
+ * ONCE and returns the first failure in the reference's order: a producer's verdict (DecodingError: the reference aborts where a
+ * verifier says no), TripleGen's decodes, RandBit's decodes and HBMPC_ZERO_SQUARE / HBMPC_NO_SQUARE_ROOT, PRandBit's decodes.
+ * capture() / replay() as for the PRandBit handle. */
+ShareErrorCode hbmpc_pipe_fixedprep_create(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl, size_t n, size_t t, size_t n_prandbit, size_t n_prandint,
+                                           size_t lk_bits, void* stream, hbmpc_pipe** pipe_out);
+/* N multiplications' worth from the front of the pools (mod.rs:1036-1040: f bits and one integer each; fpmul.rs's r_bits order):
+ *   rbits_dst [n][m][N]:  rbits_dst[p][j][i] = r_bits[p][cursor + i m + j]        rint_dst [n][N]:  rint_dst[p][i] = r_int[p][cursor + i]
+ * as ONE hbmpc_dev_take_rows of two slices on the handle's stream (a consumer on another stream orders itself after it).  The
+ * destinations are device pointers of the Fr context -- in practice hbmpc_pipe_buffer(fpmul or truncpr, "rbits" / "rint") -- and either
+ * may be null: that pool is then left alone.  Checked in this order, before anything is enqueued or a cursor moves: prep not null and
+ * a fixedprep handle, out / a destination not null, m >= 1, N >= 1 (InvalidInput); then m N bits and N integers are left
+ * (InsufficientShares, the reference's take_* error: nothing is written and the cursors stay).  The pools are empty until the first
+ * run(); run() and replay() refill them and reset the cursors.  available: out[0] = bits, out[1] = integers left. */
+ShareErrorCode hbmpc_pipe_fixedprep_take(hbmpc_pipe* prep, size_t m, size_t N, void* rbits_dst, void* rint_dst);
+ShareErrorCode hbmpc_pipe_fixedprep_available(hbmpc_pipe* prep, size_t out[2]);
 void hbmpc_pipe_destroy(hbmpc_pipe* pipe);
 ShareErrorCode hbmpc_pipe_part(hbmpc_pipe* pipe, const char* name, hbmpc_pipe** part_out);
 ShareErrorCode hbmpc_pipe_buffer(hbmpc_pipe* pipe, const char* name, void** dev_out, size_t* elements_out);
@@ -467,6 +519,29 @@ ShareErrorCode hbmpc_dev_check_double_share_c0_columns(hbmpc_ctx* ctx, const voi
  *   check_double_share   the same for pairs: degree t, degree 2t and equal constant terms */
 ShareErrorCode hbmpc_dev_transpose(hbmpc_ctx* ctx, const void* src_dev, size_t rows, size_t cols, size_t src_row_stride, void* dst_dev,
                                    size_t dst_row_stride, size_t batch, size_t src_batch_stride, size_t dst_batch_stride, void* stream);
+/* Taking from a pool.  A pool is a [party][len] array and a take is a slice of it for every party; for a pool of bits the take also
+ * regroups, because element i of a fixed-point multiplication owns pool bits i m .. i m + m - 1 and hbmpc_dev_fpmul_parties reads
+ * [party][m][N].  One call and ONE launch serve up to 8 slices.  For every row r < rows and every slice:
+ *   dst[r][j * (elements / group) + i] = src[r][i * group + j]      i < elements / group, j < group
+ * with row r of a slice at src + r * src_row_stride and dst + r * dst_row_stride.  group == 1 is a strided row copy.  Elements and
+ * strides are counted in the context's field element (32 or 8 bytes).
+ * Checked in this order, all before anything is enqueued, so a refused call writes nothing: the context (null: InvalidInput, nothing else
+ * is read); 1 <= count <= 8 and slices not null; 1 <= rows <= 65535; then slice by slice: src and dst not null and 8-byte aligned;
+ * elements >= 1, group >= 1, elements % group == 0; both strides >= elements; elements at most 2^31 and strides at most 2^40.  Each failure is
+ * InvalidInput.  Whether a src overlaps a dst -- of the same slice or of another one of the call -- is the caller's business: nothing
+ * is checked and the result of an overlapping call is unspecified.
+ * A group of at most 64 goes through the take kernel (csrc/kernels_take.hpp: a workgroup streams a contiguous run of tile * group
+ * elements into LDS and writes `group` runs of `tile` elements, 16 bytes per lane on both sides); a larger group (FPMul allows m up
+ * to 4096) takes hbmpc_dev_transpose's kernel, a launch per such slice -- the same bytes (csrc/take_plan.hpp has the rule). */
+typedef struct {
+    const void* src;
+    size_t src_row_stride;
+    void* dst;
+    size_t dst_row_stride;
+    size_t elements;
+    size_t group;
+} hbmpc_take_slice;
+ShareErrorCode hbmpc_dev_take_rows(hbmpc_ctx* ctx, const hbmpc_take_slice* slices, size_t count, size_t rows, void* stream);
 ShareErrorCode hbmpc_dev_check_degree(hbmpc_ctx* ctx, const void* coeffs_dev, const uint8_t* status_dev, size_t G, size_t m,
                                       size_t want_degree, uint32_t* bad_dev, void* stream);
 /* The exact-degree verdict from the top coefficient alone: top_dev[G] = coefficient want_degree of each polynomial (what

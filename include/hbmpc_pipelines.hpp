@@ -25,6 +25,8 @@
 //   PRandBitPipe   ... and to Goldilocks and GF(2^8), open r + b, finalize      fpmul/prandbitd.rs:311-356,437-446,189-211
 //                  (handles of csrc/capi_pipelines_riss.hip over an Fr and a Goldilocks context; PRandInt / PRandBit below are the
 //                  compositions of eight device calls with the prepare() / finish() seam)
+//   FixedPrep      run_preprocessing's steps 5 and 6: the PRandBit / PRandInt pools and take()   honeybadger/mod.rs:1396-1410,1951-2150
+//                  (the handle of csrc/capi_pipelines_fixedprep.hip over the same two contexts)
 //
 // run() only ENQUEUES on the stream; capture() records the same call sequence into a HIP graph after two eager runs and
 // replay() launches it -- at the batch sizes the protocols really use that removes the launch overhead that dominates.
@@ -552,6 +554,41 @@ class PRandBitPipe : public RissPipeline {
     static hbmpc_pipe* create(hbmpc_ctx* fr, hbmpc_ctx* gl, size_t n, size_t t, size_t B, size_t lk_bits, size_t open_senders, void* stream) {
         hbmpc_pipe* h = nullptr;
         pl_check(hbmpc_pipe_prandbit_create(fr, gl, n, t, B, lk_bits, open_senders, stream, &h), fr, "hbmpc_pipe_prandbit_create");
+        return h;
+    }
+};
+
+// FixedPrep (csrc/capi_pipelines_fixedprep.hip): run_preprocessing's steps 5 and 6 for all n parties -- one refill of the r_bits / r_int
+// pools that mul_fixed drains (honeybadger/mod.rs:1396-1410, 1951-2150, 1031-1045).  R = n_prandbit up to a multiple of t + 1 bits,
+// n_prandint integers; one of the two may be 0 and that half is then absent.  Inputs are the parts' (part("ransha") ... : borrowed
+// handles for hbmpc_pipe_buffer / _upload): coeffs, coeffs_t, coeffs_2t over Goldilocks and contrib of "prandbit" and "prandint".
+// take(): N multiplications' worth from the front of the pools into a consumer's rbits [n][m][N] / rint [n][N].
+class FixedPrep : public RissPipeline {
+  public:
+    FixedPrep(hbmpc_ctx* ctx_gl, hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t n_prandbit, size_t n_prandint, size_t lk_bits, void* stream)
+        : RissPipeline(ctx_gl, create(ctx_fr, ctx_gl, n, t, n_prandbit, n_prandint, lk_bits, stream), stream) {
+        if (n_prandbit) r_bits = typed<U256>("r_bits"), r_bits2 = typed<uint8_t>("r_bits2");
+        if (n_prandint) r_int = typed<U256>("r_int");
+    }
+    U256 *r_bits = nullptr, *r_int = nullptr;  // [n][R], [n][n_prandint]
+    uint8_t* r_bits2 = nullptr;                // [n][R]
+    hbmpc_pipe* part(const char* name) const {  // "ransha", "randousha", "triplegen", "randbit", "prandbit", "prandint"
+        hbmpc_pipe* p = nullptr;
+        pl_check(hbmpc_pipe_part(h_, name, &p), ctx_, name);
+        return p;
+    }
+    void deal() { pl_check(hbmpc_pipe_deal(h_), ctx_, "deal"); }      // the dealers' encodes of both producers
+    void finish() { pl_check(hbmpc_pipe_finish(h_), ctx_, "finish"); }  // everything after
+    void verdict(uint32_t out[2]) { pl_check(hbmpc_pipe_verdict(h_, out), ctx_, "verdict"); }  // both producers
+    // InsufficientShares (nothing written, the cursors unchanged) when a pool is short: returned, not thrown
+    ShareErrorCode take(size_t m, size_t N, U256* rbits_dst, U256* rint_dst) { return hbmpc_pipe_fixedprep_take(h_, m, N, rbits_dst, rint_dst); }
+    ShareErrorCode take(FpMul& consumer, size_t m, size_t N) { return take(m, N, consumer.buffer("rbits"), consumer.buffer("rint")); }
+    void available(size_t out[2]) { pl_check(hbmpc_pipe_fixedprep_available(h_, out), ctx_, "available"); }  // bits, integers left
+
+  private:
+    static hbmpc_pipe* create(hbmpc_ctx* fr, hbmpc_ctx* gl, size_t n, size_t t, size_t nb, size_t ni, size_t lk_bits, void* stream) {
+        hbmpc_pipe* h = nullptr;
+        pl_check(hbmpc_pipe_fixedprep_create(fr, gl, n, t, nb, ni, lk_bits, stream, &h), fr, "hbmpc_pipe_fixedprep_create");
         return h;
     }
 };

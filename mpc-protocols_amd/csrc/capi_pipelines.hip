@@ -494,7 +494,9 @@ extern "C" ShareErrorCode hbmpc_pipe_capture(hbmpc_pipe* pipe) {
 }
 extern "C" ShareErrorCode hbmpc_pipe_replay(hbmpc_pipe* pipe) {
     if (!pipe || !pipe->graph) return InvalidInput;
-    return hbmpc_graph_launch(pipe->ctx, pipe->graph, pipe->stream);
+    const ShareErrorCode rc = hbmpc_graph_launch(pipe->ctx, pipe->graph, pipe->stream);
+    if (rc == ShareSuccess) pipe->replayed();
+    return rc;
 }
 extern "C" ShareErrorCode hbmpc_pipe_sync(hbmpc_pipe* pipe) {
     if (!pipe) return InvalidInput;

@@ -39,6 +39,7 @@
 #include "protocol_route.hpp"
 #include "producer_route.hpp"
 #include "prandbit_route.hpp"
+#include "take_plan.hpp"
 #include "tables_sqrt.hpp"
 #include "tables_riss.hpp"
 
@@ -2075,6 +2076,41 @@ extern "C" ShareErrorCode hbmpc_dev_transpose(hbmpc_ctx* ctx, const void* src_de
     hipStream_t s = pick(ctx, stream);
     launch_transpose(is_gold(ctx) ? 1 : 4, (const uint64_t*)src_dev, rows, cols, src_row_stride, (uint64_t*)dst_dev, dst_row_stride, batch,
                      src_batch_stride, dst_batch_stride, s);
+    HIP_TRY(ctx, hipGetLastError());
+    return ShareSuccess;
+}
+// Slices of [party][len] pools, regrouped on the way: every check before the launch, so a refused call writes nothing.  A slice whose
+// group fits the take kernel's tile goes into ONE launch with the others (kernels_take.hpp); one beyond it takes launch_transpose with
+// the rows as its batch (plan_take, take_plan.hpp) -- the same bytes.
+extern "C" ShareErrorCode hbmpc_dev_take_rows(hbmpc_ctx* ctx, const hbmpc_take_slice* slices, size_t count, size_t rows, void* stream) {
+    if (!ctx) return InvalidInput;
+    if (const char* why = check_take_call(slices != nullptr, count, rows)) return fail(ctx, InvalidInput, why);
+    const size_t eb = ebytes(ctx);
+    TakeArgs args{};
+    size_t nfused = 0, tiles = 0;
+    for (size_t i = 0; i < count; ++i) {
+        const hbmpc_take_slice& sl = slices[i];
+        if (const char* why = check_take_slice(sl.src, sl.src_row_stride, sl.dst, sl.dst_row_stride, sl.elements, sl.group)) return fail(ctx, InvalidInput, why);
+        const TakePlan pl = plan_take(eb, sl.group);
+        if (pl.transpose) continue;
+        const size_t C = sl.elements / sl.group, t = (C + pl.tile - 1) / pl.tile;  // elements <= 2^31: inside the grid's x on either route
+        args.s[nfused] = TakeSliceArg{(const uint64_t*)sl.src, (uint64_t*)sl.dst, sl.src_row_stride, sl.dst_row_stride, C, (uint32_t)sl.group, (uint32_t)pl.tile};
+        ++nfused;
+        tiles = std::max(tiles, t);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = pick(ctx, stream);
+    const int ew64 = (int)(eb / 8);
+    if (nfused) launch_take_rows(ew64, args, (unsigned)tiles, (unsigned)rows, (unsigned)nfused, s);
+    for (size_t i = 0; i < count; ++i) {
+        const hbmpc_take_slice& sl = slices[i];
+        if (!plan_take(eb, sl.group).transpose) continue;
+        // dst[r][j][i] = src[r][i][j]: a C x group matrix per row, at most 65535 tiles of 16 i to a launch
+        const size_t C = sl.elements / sl.group, step = (size_t)65535 * 16;
+        for (size_t c0 = 0; c0 < C; c0 += step)
+            launch_transpose(ew64, (const uint64_t*)sl.src + c0 * sl.group * ew64, std::min(step, C - c0), sl.group, sl.group, (uint64_t*)sl.dst + c0 * ew64, C, rows,
+                             sl.src_row_stride, sl.dst_row_stride, s);
+    }
     HIP_TRY(ctx, hipGetLastError());
     return ShareSuccess;
 }

@@ -179,6 +179,9 @@ bool launch_fft1_mix_lo(int log, int cnt, const uint32_t* x, size_t xs, size_t G
 bool launch_gold_fft1_mix(int log, int cnt, const uint32_t* x, size_t xs, size_t G, int n, const uint32_t* tw, const MixOut& o, hipStream_t s);
 void launch_rows_party_major(int ew64, const uint64_t* src, size_t G, size_t K, int row0, int rows, int nother, uint64_t* dst, hipStream_t s);
 void launch_take_c0(int ew64, const uint64_t* coeffs, size_t G, int m, uint64_t* c0, hipStream_t s);
+// slices of [party][len] pools, regrouped (tu_take.hip, kernels_take.hpp; the arguments and the tile rule: take_plan.hpp)
+struct TakeArgs;
+void launch_take_rows(int ew64, const TakeArgs& a, unsigned tiles, unsigned rows, unsigned count, hipStream_t s);
 
 // element-wise share arithmetic (tu_elem.hip, kernels_elem.hpp): a lane per element; `parties` > 1: [party][N] operands, the
 // party in blockIdx.y.  grid_parties of the two kernels that loop over the parties themselves: 1 or `parties` (the caller picks by N)

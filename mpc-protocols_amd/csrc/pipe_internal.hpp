@@ -1,5 +1,5 @@
 // pipe_internal.hpp -- struct hbmpc_pipe and its helpers: what the files that implement hbmpc_pipe_* handles share
-// (capi_pipelines.hip, capi_pipelines_riss.hip).  Like them it is a CLIENT of the public header only and compiles with a host C++ compiler.
+// (capi_pipelines.hip, capi_pipelines_riss.hip, capi_pipelines_io.hip, capi_pipelines_fixedprep.hip).  Like them it is a CLIENT of the public header only and compiles with a host C++ compiler.
 #pragma once
 #include <cstring>
 #include <map>
@@ -153,6 +153,7 @@ struct hbmpc_pipe {
     virtual void deal() { throw PipeError{InvalidInput}; }
     virtual void finish() { throw PipeError{InvalidInput}; }
     virtual hbmpc_pipe* part(const std::string&) { return nullptr; }
+    virtual void replayed() {}  // hbmpc_pipe_replay has enqueued the recording: host-side state that run() resets (fixedprep's cursors)
     virtual void verdict(uint32_t out[2]) {
         if (!bad) throw PipeError{InvalidInput};
         PL(hbmpc_memcpy_d2h(ctx, out, bad, 8, stream));

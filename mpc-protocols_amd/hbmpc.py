@@ -83,6 +83,12 @@ FUSED_PRODUCERS_DEFAULT = {"fr": 256, "goldilocks": 256}  # hbmpc_set_fused_prod
 FUSED_PRANDBIT_DEFAULT = 256  # hbmpc_set_fused_prandbit's default (FUSED_PRANDBIT, csrc/hbmpc_capi.hip)
 
 
+class TakeSlice(C.Structure):
+    """hbmpc_take_slice: one slice of hbmpc_dev_take_rows (Engine.take_rows)"""
+    _fields_ = [("src", C.c_void_p), ("src_row_stride", C.c_size_t), ("dst", C.c_void_p), ("dst_row_stride", C.c_size_t),
+                ("elements", C.c_size_t), ("group", C.c_size_t)]
+
+
 def fixed_point_reciprocal_scaled(denom, f):
     """(rc, w, first_bad): hbmpc_fixed_point_reciprocal_scaled -- fpdiv/mod.rs:8-60 for N denominators ([N] U256 -> [N] U256); host
     only, needs no device.  first_bad: the index of the first invalid divisor, or None"""
@@ -447,6 +453,13 @@ class Engine:
         return self.L.hbmpc_dev_transpose(self.ctx, C.c_void_p(src_d), C.c_size_t(rows), C.c_size_t(cols), C.c_size_t(src_row_stride),
                                           C.c_void_p(dst_d), C.c_size_t(dst_row_stride), C.c_size_t(batch), C.c_size_t(src_batch_stride),
                                           C.c_size_t(dst_batch_stride), C.c_void_p(stream))
+
+    def take_rows(self, slices, rows, stream=0):
+        """hbmpc_dev_take_rows: slices = [(src_d, src_row_stride, dst_d, dst_row_stride, elements, group), ...] (at most 8; device pointers
+        as ints, strides and elements in this engine's field element): dst[r][j * (elements / group) + i] = src[r][i * group + j] for
+        every row r < rows -- one launch for all of them"""
+        arr = (TakeSlice * max(len(slices), 1))(*[TakeSlice(*[int(x) if x is not None else None for x in s]) for s in slices])
+        return self.L.hbmpc_dev_take_rows(self.ctx, arr, C.c_size_t(len(slices)), C.c_size_t(rows), C.c_void_p(stream))
 
     def dev_check_degree(self, coeffs_d, status_d, G, m, want_degree, bad_d, stream=0):
         return self.L.hbmpc_dev_check_degree(self.ctx, C.c_void_p(coeffs_d), C.c_void_p(status_d), C.c_size_t(G), C.c_size_t(m),

@@ -24,6 +24,8 @@ in the library; this file only names things for the tests and bench.py.
   PRandBit       ... and to Goldilocks and GF(2^8), open r + b, finalize   fpmul/prandbitd.rs:311-356,437-446,189-211
   PRandIntPipe / PRandBitPipe  the same two over the hbmpc_pipe_prandint / _prandbit handles: run() is ONE device call
                  (hbmpc_dev_prandint_parties / hbmpc_dev_prandbit_parties), one launch for a small batch
+  FixedPrep      run_preprocessing's steps 5 and 6: RanSha -> RanDouSha -> TripleGen -> RandBit over Goldilocks, PRandBit / PRandInt over
+                 Fr, and take() from the pools they fill          honeybadger/mod.rs:1396-1410, 1951-2150, 1031-1045 (csrc/capi_pipelines_fixedprep.hip)
 PRandInt and PRandBit are the compositions of eight device calls over two contexts (their prepare() / finish() seam lets a test stand
 between the parties' messages and the open); PRandIntPipe and PRandBitPipe are the handles (csrc/capi_pipelines_riss.hip).
 """
@@ -401,9 +403,9 @@ class RandBit(_Pipe):
 
     ZERO_SQUARE, NO_SQUARE_ROOT = 102, 103
 
-    def __init__(self, eng, n, t, N, stream=0):
+    def __init__(self, eng, n, t, N, stream=0, _handle=None):
         self.n, self.t, self.N = n, t, N
-        super().__init__(eng, self._create(eng, "hbmpc_pipe_randbit_create", n, t, N, stream=stream), stream)
+        super().__init__(eng, _handle or self._create(eng, "hbmpc_pipe_randbit_create", n, t, N, stream=stream), stream)
 
     def upload(self, a, ta, tb, tc):
         for name, src in (("a", a), ("ta", ta), ("tb", tb), ("tc", tc)):
@@ -456,10 +458,11 @@ class PRandIntPipe(_RissPipe):
     (hbmpc_dev_prandint_parties): ONE launch up to hbmpc_set_fused_prandbit chunks of t + 1 elements for the shapes whose tables fit a
     workgroup's LDS, two launches otherwise."""
 
-    def __init__(self, eng_fr, n, t, B, lk_bits, stream=0):
+    def __init__(self, eng_fr, n, t, B, lk_bits, stream=0, _handle=None):
         self.n, self.t, self.B, self.lk_bits = n, t, B, lk_bits
-        h = C.c_void_p()
-        rc = eng_fr.L.hbmpc_pipe_prandint_create(eng_fr.ctx, *[C.c_size_t(v) for v in (n, t, B, lk_bits)], C.c_void_p(stream), C.byref(h))
+        h = _handle or C.c_void_p()
+        rc = 0 if _handle else eng_fr.L.hbmpc_pipe_prandint_create(eng_fr.ctx, *[C.c_size_t(v) for v in (n, t, B, lk_bits)], C.c_void_p(stream),
+                                                                   C.byref(h))
         if rc != 0:
             raise RuntimeError(f"hbmpc_pipe_prandint_create{(n, t, B, lk_bits)} -> ShareErrorCode {rc}: {eng_fr.last_error()}")
         super().__init__(eng_fr, h, stream)
@@ -473,13 +476,14 @@ class PRandBitPipe(_RissPipe):
     library call (hbmpc_dev_prandbit_parties): ONE launch up to hbmpc_set_fused_prandbit chunks when the open has exactly 2t + 1 senders
     and the tables fit a workgroup's LDS ((4,1) .. (12,3)), eight launches otherwise."""
 
-    def __init__(self, eng_gl, eng_fr, n, t, B, lk_bits, stream=0, open_senders=None):
+    def __init__(self, eng_gl, eng_fr, n, t, B, lk_bits, stream=0, open_senders=None, _handle=None):
         self.n, self.t, self.B, self.lk_bits, self.G = n, t, B, lk_bits, B // (t + 1)
         self.open_senders = 2 * t + 1 if open_senders is None else open_senders
         self.fr = eng_fr
-        h = C.c_void_p()
-        rc = eng_fr.L.hbmpc_pipe_prandbit_create(eng_fr.ctx, eng_gl.ctx, *[C.c_size_t(v) for v in (n, t, B, lk_bits, self.open_senders)],
-                                                 C.c_void_p(stream), C.byref(h))
+        h = _handle or C.c_void_p()
+        rc = 0 if _handle else eng_fr.L.hbmpc_pipe_prandbit_create(eng_fr.ctx, eng_gl.ctx,
+                                                                   *[C.c_size_t(v) for v in (n, t, B, lk_bits, self.open_senders)],
+                                                                   C.c_void_p(stream), C.byref(h))
         if rc != 0:
             raise RuntimeError(f"hbmpc_pipe_prandbit_create{(n, t, B, lk_bits, self.open_senders)} -> ShareErrorCode {rc}: {eng_fr.last_error()}")
         super().__init__(eng_gl, h, stream)  # the handle's own context is the Goldilocks one (the open's decode counters are its)
@@ -487,6 +491,74 @@ class PRandBitPipe(_RissPipe):
     def open_summary(self):
         """(n_fallback, n_failed, first_failed, first_error) of the two decodes of the open"""
         return [tuple(int(v) for v in self.download_named(k).view(np.uint32)) for k in ("summary_first", "summary")]
+
+
+class FixedPrep(_RissPipe):
+    """The second half of run_preprocessing (honeybadger/mod.rs:1396-1410, 1951-2150) for all n parties as one handle
+    (hbmpc_pipe_fixedprep_create): one refill of the r_bits / r_int pools that mul_fixed drains, from the dealers' Goldilocks polynomials
+    and the RISS contributions.  Sizes (the reference's arithmetic): R = n_prandbit up to a multiple of t + 1, T = R up to a multiple of
+    2t + 1, K1 = ceil((R + 2T) / (n - 2t)) RanSha columns per dealer, K2 = ceil(T / (t + 1)) RanDouSha columns.  Parts (borrowed): rs, rd,
+    tg, rb over Goldilocks, pb (PRandBitPipe), pi (PRandIntPipe); None where that half is absent.  Buffers r_bits [n][R] U256, r_bits2
+    [n][R] bytes, r_int [n][n_prandint] U256.  deal() / finish() are the halves of run(); take(consumer, N) moves N elements' worth from
+    the front of the pools into an FpMul / TruncPr handle's rbits / rint."""
+    _EB = {"r_bits": 32, "r_bits2": 1, "r_int": 32}
+
+    @staticmethod
+    def sizes(n, t, n_prandbit):
+        """(R, T, K1, K2)"""
+        R = -(-n_prandbit // (t + 1)) * (t + 1)
+        T = -(-R // (2 * t + 1)) * (2 * t + 1)
+        return R, T, -(-(R + 2 * T) // (n - 2 * t)), -(-T // (t + 1))
+
+    def __init__(self, eng_gl, eng_fr, n, t, n_prandbit, n_prandint, lk_bits, stream=0):
+        self.n, self.t, self.n_prandbit, self.n_prandint, self.lk_bits, self.fr = n, t, n_prandbit, n_prandint, lk_bits, eng_fr
+        h = C.c_void_p()
+        rc = eng_fr.L.hbmpc_pipe_fixedprep_create(eng_fr.ctx, eng_gl.ctx, *[C.c_size_t(v) for v in (n, t, n_prandbit, n_prandint, lk_bits)],
+                                                  C.c_void_p(stream), C.byref(h))
+        if rc != 0:
+            raise RuntimeError(f"hbmpc_pipe_fixedprep_create{(n, t, n_prandbit, n_prandint, lk_bits)} -> ShareErrorCode {rc}: {eng_fr.last_error()}")
+        super().__init__(eng_gl, h, stream)
+        self.rs = self.rd = self.tg = self.rb = self.pb = self.pi = None
+        if n_prandbit:
+            self.R, self.T, self.K1, self.K2 = self.sizes(n, t, n_prandbit)
+            self.rs = RanSha(eng_gl, n, t, self.K1, stream, _handle=self._part("ransha"))
+            self.rd = RanDouSha(eng_gl, n, t, self.K2, stream, _handle=self._part("randousha"))
+            self.tg = TripleGen(eng_gl, n, t, self.T, stream, _handle=self._part("triplegen"))
+            self.rb = RandBit(eng_gl, n, t, self.R, stream, _handle=self._part("randbit"))
+            self.pb = PRandBitPipe(eng_gl, eng_fr, n, t, self.R, lk_bits, stream, _handle=self._part("prandbit"))
+        if n_prandint:
+            self.pi = PRandIntPipe(eng_fr, n, t, n_prandint, lk_bits, stream, _handle=self._part("prandint"))
+        for part in (self.rs, self.rd, self.tg, self.rb, self.pb, self.pi):
+            if part is not None:
+                part._own = False  # borrowed: destroyed with this handle
+
+    _part = Preprocessing._part
+
+    def deal(self):
+        self._call("hbmpc_pipe_deal", False)
+
+    def finish(self, check=False):
+        self._call("hbmpc_pipe_finish", check)
+
+    def verdict(self):
+        return self._bad()
+
+    def available(self):
+        """(bits, integers) left in the pools"""
+        out = (C.c_size_t * 2)()
+        self._rc(self.eng.L.hbmpc_pipe_fixedprep_available(self.h, out), "available")
+        return int(out[0]), int(out[1])
+
+    def take_raw(self, m, N, rbits_d, rint_d):
+        """hbmpc_pipe_fixedprep_take -> ShareErrorCode (1 = InsufficientShares: nothing written, cursors unchanged)"""
+        return self.eng.L.hbmpc_pipe_fixedprep_take(self.h, C.c_size_t(m), C.c_size_t(N), C.c_void_p(rbits_d or None), C.c_void_p(rint_d or None))
+
+    def take(self, consumer, N=None):
+        """N (default: all of the consumer's) elements' worth into consumer.rbits [n][m][N] and consumer.rint [n][N]; the consumer (FpMul,
+        TruncPr, FpDivConst) holds exactly N elements"""
+        N = consumer.N if N is None else N
+        assert N == consumer.N, "the consumer's rbits are [n][m][N] for its own N"
+        self._rc(self.take_raw(consumer.m, N, consumer.rbits, consumer.rint), "take")
 
 
 class _Riss:

@@ -404,6 +404,22 @@ impl GpuShares {
         let rc = unsafe { sys::hbmpc_pipe_prandint_create(self.ctx, n, t, batch, l_plus_k, stream, &mut p) };
         self.wrap(rc, p, n)
     }
+    /// FixedPrep for all n parties: run_preprocessing's steps 5 and 6 (honeybadger/mod.rs:1396-1410, 1951-2150) -- one refill of the
+    /// r_bits / r_int pools that `mul_fixed` drains (:1031-1045).  `self` is the bls12-381 Fr context, `gl` a Goldilocks context on the same
+    /// device; one of `n_prandbit` / `n_prandint` may be 0.  Parts `"ransha"`, `"randousha"`, `"triplegen"`, `"randbit"`, `"prandbit"`,
+    /// `"prandint"` (`part`); buffers r_bits, r_int (`download`), r_bits2 (`download_bytes`); `take` / `available` drain the pools
+    pub fn pipe_fixedprep<'a>(&'a self, gl: &'a GpuShares, n: usize, t: usize, n_prandbit: usize, n_prandint: usize, l_plus_k: usize,
+                              stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'a>, InterpolateError> {
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_fixedprep_create(self.ctx, gl.ctx, n, t, n_prandbit, n_prandint, l_plus_k, stream, &mut p) };
+        self.wrap(rc, p, n)
+    }
+    /// hbmpc_dev_take_rows: slices of `[party][len]` pools, regrouped, in one launch (at most 8 slices).  Safety: every pointer of every
+    /// slice is a device buffer that holds `rows` rows at its stride
+    pub unsafe fn take_rows(&self, slices: &[sys::TakeSlice], rows: usize, stream: *mut core::ffi::c_void) -> Result<(), InterpolateError> {
+        let rc = sys::hbmpc_dev_take_rows(self.ctx, slices.as_ptr(), slices.len(), rows, stream);
+        self.check(rc, rows)
+    }
 }
 
 impl<'a> GpuPipeline<'a> {
@@ -505,6 +521,21 @@ impl<'a> GpuPipeline<'a> {
             sys::HBMPC_NO_SQUARE_ROOT => Err(RandBitError::SquareRoot),
             _ => Err(RandBitError::Abort),
         }
+    }
+    /// a FixedPrep pipeline (`pipe_fixedprep`): `pairs` multiplications' worth from the front of its pools into a consumer's buffers --
+    /// `rbits` [n][m][pairs] and `rint` [n][pairs] of an fpmul or truncpr pipeline (`buffer`), either may be null.  A pool that is short
+    /// is `InsufficientShares`, as the reference's take_* : nothing is written and the cursors stay.
+    /// Safety: the destinations are device buffers of those sizes
+    pub unsafe fn take(&self, m: usize, pairs: usize, rbits: *mut sys::U256, rint: *mut sys::U256) -> Result<(), InterpolateError> {
+        let rc = sys::hbmpc_pipe_fixedprep_take(self.pipe, m, pairs, rbits as *mut core::ffi::c_void, rint as *mut core::ffi::c_void);
+        self.gpu.check(rc, 0)
+    }
+    /// (bits, integers) left in a FixedPrep pipeline's pools
+    pub fn available(&self) -> Result<(usize, usize), InterpolateError> {
+        let mut left = [0usize; 2];
+        let rc = unsafe { sys::hbmpc_pipe_fixedprep_available(self.pipe, left.as_mut_ptr()) };
+        self.gpu.check(rc, 0)?;
+        Ok((left[0], left[1]))
     }
     /// the two halves of a producer's run: the dealers' `compute_shares`, then everything after their messages have arrived
     pub fn deal(&self) -> Result<(), InterpolateError> {
