@@ -337,6 +337,24 @@ ShareErrorCode hbmpc_pipe_fixedprep_create(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl,
  * run(); run() and replay() refill them and reset the cursors.  available: out[0] = bits, out[1] = integers left. */
 ShareErrorCode hbmpc_pipe_fixedprep_take(hbmpc_pipe* prep, size_t m, size_t N, void* rbits_dst, void* rint_dst);
 ShareErrorCode hbmpc_pipe_fixedprep_available(hbmpc_pipe* prep, size_t out[2]);
+/* The seeded forms of the three handles above: the RISS contributions are drawn on the device from one 32-byte seed per sender
+ * (contract "hbmpc-riss-chacha20-v1" and its SECURITY note: hbmpc_dev_riss_sample below), and run() is
+ * hbmpc_dev_prandbit_parties_seeded / hbmpc_dev_prandint_parties_seeded.  Same arguments, checks and buffers as the unseeded creates,
+ * except: there is a buffer seeds ([n][32] bytes, counted in bytes) and NO contrib -- `contrib` is an unknown name and nothing of its
+ * size is allocated, so (16, 5) at 2^16 elements is a handle of sums' size.  A handle has a stream index, 0 at creation:
+ * hbmpc_pipe_set_stream_index sets it (InvalidInput for any other handle), run() draws at [index, index + B) and then advances the
+ * index by B -- B for PRandBit, n_prandint for PRandInt -- so consecutive runs never reuse a position; a run() that is refused leaves
+ * it.  A seeded fixedprep's parts "prandbit" and "prandint" are seeded handles; before each of them runs, fixedprep copies its own
+ * seeds buffer and index to it (the two draw in domains 0 and 1, so they may share both), and then advances its own index by
+ * max(R, n_prandint).  Known limit: hbmpc_pipe_capture on a seeded handle returns InvalidInput (hbmpc_last_error says why): a
+ * replayed graph would draw the same stream positions again at every replay. */
+ShareErrorCode hbmpc_pipe_prandbit_create_seeded(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl, size_t n, size_t t, size_t B, size_t lk_bits,
+                                                 size_t open_senders, void* stream, hbmpc_pipe** pipe_out);
+ShareErrorCode hbmpc_pipe_prandint_create_seeded(hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t B, size_t lk_bits, void* stream,
+                                                 hbmpc_pipe** pipe_out);
+ShareErrorCode hbmpc_pipe_fixedprep_create_seeded(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl, size_t n, size_t t, size_t n_prandbit,
+                                                  size_t n_prandint, size_t lk_bits, void* stream, hbmpc_pipe** pipe_out);
+ShareErrorCode hbmpc_pipe_set_stream_index(hbmpc_pipe* pipe, uint64_t index);
 void hbmpc_pipe_destroy(hbmpc_pipe* pipe);
 ShareErrorCode hbmpc_pipe_part(hbmpc_pipe* pipe, const char* name, hbmpc_pipe** part_out);
 ShareErrorCode hbmpc_pipe_buffer(hbmpc_pipe* pipe, const char* name, void** dev_out, size_t* elements_out);
@@ -1183,7 +1201,8 @@ ShareErrorCode hbmpc_gl_dev_randbit_parties(hbmpc_ctx* ctx, const uint64_t* a, c
  * (PRandInt).  Every party sends a value r_T <= 2^(l+k) per maximal unqualified set T (the t-subsets of 0..n) to the parties outside
  * T; the sums over the n senders are the replicated shares, converted locally to Shamir shares in each field.  A folded r_T is a
  * plain integer below 2^62, one uint64_t, in either field.  Supported shapes: n >= 3t + 1 and C(n, t) <= 8192 (and C(n, t) n <= 2^20
- * table entries); others return InvalidInput.  Not here: sampling the r_T, sessions, messages.
+ * table entries); others return InvalidInput.  Not here: sessions, messages.  Sampling the r_T: the seeded calls at the end of this
+ * section draw them from a keyed stream of the library's own; a caller with an rng of its own passes contrib.
  * Coefficient tables are built per context and (n, t) at the first call (run it once before a graph capture). */
 /* the sets in the order every call below indexes them: combinations(0..n, t), lexicographic (prandbitd.rs:479).  *count_out = C(n, t)
  * (InvalidInput beyond 8192); ids_out (nullable) receives count x t ids.  Host only: needs no context and no device. */
@@ -1247,6 +1266,54 @@ ShareErrorCode hbmpc_set_fused_prandbit(hbmpc_ctx* ctx_fr, size_t max_chunks);
 /* A/B aid: how the conversion lays its work out.  0 = by size (default), 1 = always a workgroup per 64 elements and 16 parties,
  * 2 = always a workgroup per 64 elements and party with the sets in four slices.  Same results. */
 ShareErrorCode hbmpc_set_riss_form(hbmpc_ctx* ctx, int form);
+
+/* ---- seeded RISS dealing: the r_T are drawn ON THE DEVICE (csrc/kernels_riss_sample.hpp) ------------------------------------------
+ * contrib [n][C(n,t)][B] is by far the largest input of the library ((16, 5): 16 x 4368 x B x 8 bytes), its values are uniform
+ * random numbers, and only their sums over the senders are ever used.  These calls draw them from a keyed stream this library
+ * defines, so a device-resident dealer needs no host rng and no upload, and the all-parties calls never materialise contrib.
+ * Contract "hbmpc-riss-chacha20-v1" (restated in tests/riss_seeded_model.py): the value of (seed, domain, set index T, element index
+ * i, lk_bits) is
+ *     for attempt = 0, 1, ...:
+ *         blk = ChaCha20 block (RFC 8439 block function, 20 rounds; key = seed as eight little-endian words;
+ *                               state words 12..15 = (attempt, T | domain << 16, i mod 2^32, i div 2^32))
+ *         for c = 0 .. 7:  v = (blk[2c] | blk[2c+1] << 32) & (2^(lk_bits+1) - 1);  if v <= 2^lk_bits: return v
+ * -- uniform over the reference's range [0, 2^(l+k)], bound included (prandbitd.rs:518, :766-771), by rejection; one block chain per
+ * value.  T is the index in hbmpc_riss_tsets order (below 8192, so 16 bits); domain (at most 65535) separates uses of one seed: the
+ * protocol calls use 0 for PRandBit and 1 for PRandInt, so the two halves of FixedPrep may share one set of seeds; i = first_index + b.
+ * This is NOT the stream of the reference's rng (generate_riss draws from the node's rng through gen_big_uint_range,
+ * prandbitd.rs:534-539, :766-784): a deployment that needs bit-equality with a given Rust rng keeps drawing on the host and passes
+ * contrib to the unseeded calls.
+ * SECURITY: ONE SEED PER SENDER -- a sender's values are its secret, and a seed shared by two senders makes them the same party.  A
+ * (seed, domain, index) range must NEVER be reused: the same positions give the same r_T, and shares of two batches that reuse them
+ * differ by public values only.  Nothing in the library can detect either; take first_index from a counter that only grows (the
+ * seeded handles do).  sums and one sender's rows hold secrets, and they and the library's staging buffers are recycled without
+ * being cleared.
+ * hbmpc_dev_riss_sample: ONE sender's contributions, what a deployed node sends -- out_dev [C(n,t)][B] u64, row T for the parties
+ * outside T -- for a context of either field; hbmpc_riss_sample is its host-pointer form (the rows staged back like every host form).
+ * hbmpc_dev_riss_sample_fold: seeds_dev [n][8] uint32_t in device memory (n 32-byte seeds; sender s's key words are seeds_dev[8 s ..])
+ * -> sums_out [C(n,t)][B], the sums over all n senders, drawn and added in registers.  It equals hbmpc_dev_riss_fold over the n
+ * hbmpc_dev_riss_sample outputs byte for byte, with every verdict byte zero: a drawn value is within the bound by construction.
+ * Checked before the first launch, in this order (a refused call writes nothing): ctx null, the shape (n >= 3t + 1, C(n, t) <= 8192)
+ * -> InvalidInput; lk_bits + 2 + ceil(log2 n) >= 64 -> HBMPC_FIELD_CAPACITY; B > 2^32 or beyond the grid, domain > 65535,
+ * first_index + B passing 2^64 -> InvalidInput; B = 0 -> ShareSuccess; null seed or buffer -> InvalidInput. */
+ShareErrorCode hbmpc_dev_riss_sample(hbmpc_ctx* ctx, const uint8_t seed[32], size_t n, size_t t, size_t domain, size_t B, uint64_t first_index,
+                                     size_t lk_bits, uint64_t* out_dev, void* stream);
+ShareErrorCode hbmpc_riss_sample(hbmpc_ctx* ctx, const uint8_t seed[32], size_t n, size_t t, size_t domain, size_t B, uint64_t first_index,
+                                 size_t lk_bits, uint64_t* out);
+ShareErrorCode hbmpc_dev_riss_sample_fold(hbmpc_ctx* ctx, const uint32_t* seeds_dev, size_t n, size_t t, size_t domain, size_t B,
+                                          uint64_t first_index, size_t lk_bits, uint64_t* sums_out, void* stream);
+/* hbmpc_dev_prandbit_parties / hbmpc_dev_prandint_parties with contrib replaced by (seeds_dev, first_index): hbmpc_dev_riss_sample_fold
+ * in domain 0 (PRandBit) or 1 (PRandInt) writes sums, bad is set to zeros, and then exactly the launches the unseeded call runs after
+ * its fold -- so every output buffer holds the bytes the unseeded call writes when it is given the materialised contrib.  Always the
+ * separate launches: the one-launch form reads contrib, and hbmpc_set_fused_prandbit is not consulted.  The unseeded calls' checks in
+ * their order, with first_index + B passing 2^64 (InvalidInput) after them and before B = 0. */
+ShareErrorCode hbmpc_dev_prandbit_parties_seeded(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl, const uint32_t* seeds_dev, uint64_t first_index,
+                                                 const uint64_t* b_q, size_t n, size_t t, size_t B, size_t lk_bits, size_t open_senders,
+                                                 uint64_t* sums, uint8_t* bad, U256* r_p, uint8_t* r_2, uint64_t* r_q, uint64_t* rb, uint64_t* y_ws,
+                                                 uint64_t* z_ws, uint64_t* opened, U256* b_p, uint8_t* b_2, uint8_t* rstatus,
+                                                 hbmpc_recover_summary* summary_first, hbmpc_recover_summary* summary, void* stream);
+ShareErrorCode hbmpc_dev_prandint_parties_seeded(hbmpc_ctx* ctx_fr, const uint32_t* seeds_dev, uint64_t first_index, size_t n, size_t t, size_t B,
+                                                 size_t lk_bits, uint64_t* sums, uint8_t* bad, U256* r_p, void* stream);
 
 /* ---- A/B aid: 0 = unsaturated 9x29-bit limbs (default, fast), 1 = saturated 8x32-bit limbs
  * (the straightforward formulation; same results, kept as a cross-check). */

@@ -502,6 +502,9 @@ class PRandBit : public PRandInt {
 // The same two as hbmpc_pipe handles (csrc/capi_pipelines_riss.hip): run() is ONE device call (hbmpc_dev_prandint_parties /
 // hbmpc_dev_prandbit_parties: one launch for a small batch), capture() / replay() work as for the other handles.  Every buffer has an
 // element type of its own, which the typed accessors below count in.
+// seeded = true (hbmpc_pipe_*_create_seeded; contract "hbmpc-riss-chacha20-v1", include/hbmpc_hip.h): the handle has seeds ([n][32]
+// bytes, one seed per sender) and no contrib (the pointer is null); run() draws the contributions on the device at the handle's stream
+// index and advances it (set_stream_index); capture() throws: a replayed graph would reuse the same stream positions.
 class RissPipeline : public Pipeline {
   public:
     template <class T>
@@ -512,6 +515,7 @@ class RissPipeline : public Pipeline {
     void upload_typed(const char* name, const T* src, size_t elements) { pl_check(hbmpc_pipe_upload(h_, name, src, elements), ctx_, name); }
     template <class T>
     void download_typed(const char* name, T* dst, size_t elements) { pl_check(hbmpc_pipe_download(h_, name, dst, elements), ctx_, name); }
+    void set_stream_index(uint64_t index) { pl_check(hbmpc_pipe_set_stream_index(h_, index), ctx_, "set_stream_index"); }  // seeded handles
 
   protected:
     using Pipeline::Pipeline;
@@ -520,18 +524,20 @@ class RissPipeline : public Pipeline {
 // contrib [n][C(n,t)][B] -> sums [C(n,t)][B], bad [n][C(n,t)] bytes, r_p [n][B] (prandbitd.rs:667-684, 311-356).  Any B.
 class PRandIntPipe : public RissPipeline {
   public:
-    PRandIntPipe(hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t B, size_t lk_bits, void* stream)
-        : RissPipeline(ctx_fr, create(ctx_fr, n, t, B, lk_bits, stream), stream) {
-        contrib = typed<uint64_t>("contrib"), sums = typed<uint64_t>("sums"), bad = typed<uint8_t>("bad"), r_p = typed<U256>("r_p");
+    PRandIntPipe(hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t B, size_t lk_bits, void* stream, bool seeded = false)
+        : RissPipeline(ctx_fr, create(ctx_fr, n, t, B, lk_bits, stream, seeded), stream) {
+        contrib = seeded ? nullptr : typed<uint64_t>("contrib"), seeds = seeded ? typed<uint8_t>("seeds") : nullptr;
+        sums = typed<uint64_t>("sums"), bad = typed<uint8_t>("bad"), r_p = typed<U256>("r_p");
     }
     uint64_t *contrib, *sums;
-    uint8_t* bad;
+    uint8_t *bad, *seeds;
     U256* r_p;
 
   private:
-    static hbmpc_pipe* create(hbmpc_ctx* ctx, size_t n, size_t t, size_t B, size_t lk_bits, void* stream) {
+    static hbmpc_pipe* create(hbmpc_ctx* ctx, size_t n, size_t t, size_t B, size_t lk_bits, void* stream, bool seeded) {
         hbmpc_pipe* h = nullptr;
-        pl_check(hbmpc_pipe_prandint_create(ctx, n, t, B, lk_bits, stream, &h), ctx, "hbmpc_pipe_prandint_create");
+        if (seeded) pl_check(hbmpc_pipe_prandint_create_seeded(ctx, n, t, B, lk_bits, stream, &h), ctx, "hbmpc_pipe_prandint_create_seeded");
+        else pl_check(hbmpc_pipe_prandint_create(ctx, n, t, B, lk_bits, stream, &h), ctx, "hbmpc_pipe_prandint_create");
         return h;
     }
 };
@@ -540,20 +546,25 @@ class PRandIntPipe : public RissPipeline {
 // t + 1; open_senders: 0 = the reference's 2t + 1 (no OEC round).  last_summary() is the revealed values' decode's.
 class PRandBitPipe : public RissPipeline {
   public:
-    PRandBitPipe(hbmpc_ctx* ctx_gl, hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t B, size_t lk_bits, void* stream, size_t open_senders = 0)
-        : RissPipeline(ctx_gl, create(ctx_fr, ctx_gl, n, t, B, lk_bits, open_senders, stream), stream) {
-        contrib = typed<uint64_t>("contrib"), b_q = typed<uint64_t>("b_q"), sums = typed<uint64_t>("sums"), r_q = typed<uint64_t>("r_q");
+    PRandBitPipe(hbmpc_ctx* ctx_gl, hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t B, size_t lk_bits, void* stream, size_t open_senders = 0,
+                 bool seeded = false)
+        : RissPipeline(ctx_gl, create(ctx_fr, ctx_gl, n, t, B, lk_bits, open_senders, stream, seeded), stream) {
+        contrib = seeded ? nullptr : typed<uint64_t>("contrib"), seeds = seeded ? typed<uint8_t>("seeds") : nullptr;
+        b_q = typed<uint64_t>("b_q"), sums = typed<uint64_t>("sums"), r_q = typed<uint64_t>("r_q");
         rb = typed<uint64_t>("rb"), opened = typed<uint64_t>("opened"), bad = typed<uint8_t>("bad"), r_2 = typed<uint8_t>("r_2");
         b_2 = typed<uint8_t>("b_2"), rstatus = typed<uint8_t>("rstatus"), r_p = typed<U256>("r_p"), b_p = typed<U256>("b_p");
     }
     uint64_t *contrib, *b_q, *sums, *r_q, *rb, *opened;
-    uint8_t *bad, *r_2, *b_2, *rstatus;
+    uint8_t *bad, *r_2, *b_2, *rstatus, *seeds;
     U256 *r_p, *b_p;
 
   private:
-    static hbmpc_pipe* create(hbmpc_ctx* fr, hbmpc_ctx* gl, size_t n, size_t t, size_t B, size_t lk_bits, size_t open_senders, void* stream) {
+    static hbmpc_pipe* create(hbmpc_ctx* fr, hbmpc_ctx* gl, size_t n, size_t t, size_t B, size_t lk_bits, size_t open_senders, void* stream,
+                              bool seeded) {
         hbmpc_pipe* h = nullptr;
-        pl_check(hbmpc_pipe_prandbit_create(fr, gl, n, t, B, lk_bits, open_senders, stream, &h), fr, "hbmpc_pipe_prandbit_create");
+        if (seeded)
+            pl_check(hbmpc_pipe_prandbit_create_seeded(fr, gl, n, t, B, lk_bits, open_senders, stream, &h), fr, "hbmpc_pipe_prandbit_create_seeded");
+        else pl_check(hbmpc_pipe_prandbit_create(fr, gl, n, t, B, lk_bits, open_senders, stream, &h), fr, "hbmpc_pipe_prandbit_create");
         return h;
     }
 };
@@ -565,11 +576,15 @@ class PRandBitPipe : public RissPipeline {
 // take(): N multiplications' worth from the front of the pools into a consumer's rbits [n][m][N] / rint [n][N].
 class FixedPrep : public RissPipeline {
   public:
-    FixedPrep(hbmpc_ctx* ctx_gl, hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t n_prandbit, size_t n_prandint, size_t lk_bits, void* stream)
-        : RissPipeline(ctx_gl, create(ctx_fr, ctx_gl, n, t, n_prandbit, n_prandint, lk_bits, stream), stream) {
+    // seeded: "prandbit" and "prandint" are seeded handles fed from this handle's own seeds and stream index; no contrib anywhere
+    FixedPrep(hbmpc_ctx* ctx_gl, hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t n_prandbit, size_t n_prandint, size_t lk_bits, void* stream,
+              bool seeded = false)
+        : RissPipeline(ctx_gl, create(ctx_fr, ctx_gl, n, t, n_prandbit, n_prandint, lk_bits, stream, seeded), stream) {
         if (n_prandbit) r_bits = typed<U256>("r_bits"), r_bits2 = typed<uint8_t>("r_bits2");
         if (n_prandint) r_int = typed<U256>("r_int");
+        if (seeded) seeds = typed<uint8_t>("seeds");
     }
+    uint8_t* seeds = nullptr;  // [n][32] (seeded)
     U256 *r_bits = nullptr, *r_int = nullptr;  // [n][R], [n][n_prandint]
     uint8_t* r_bits2 = nullptr;                // [n][R]
     hbmpc_pipe* part(const char* name) const {  // "ransha", "randousha", "triplegen", "randbit", "prandbit", "prandint"
@@ -586,9 +601,10 @@ class FixedPrep : public RissPipeline {
     void available(size_t out[2]) { pl_check(hbmpc_pipe_fixedprep_available(h_, out), ctx_, "available"); }  // bits, integers left
 
   private:
-    static hbmpc_pipe* create(hbmpc_ctx* fr, hbmpc_ctx* gl, size_t n, size_t t, size_t nb, size_t ni, size_t lk_bits, void* stream) {
+    static hbmpc_pipe* create(hbmpc_ctx* fr, hbmpc_ctx* gl, size_t n, size_t t, size_t nb, size_t ni, size_t lk_bits, void* stream, bool seeded) {
         hbmpc_pipe* h = nullptr;
-        pl_check(hbmpc_pipe_fixedprep_create(fr, gl, n, t, nb, ni, lk_bits, stream, &h), fr, "hbmpc_pipe_fixedprep_create");
+        if (seeded) pl_check(hbmpc_pipe_fixedprep_create_seeded(fr, gl, n, t, nb, ni, lk_bits, stream, &h), fr, "hbmpc_pipe_fixedprep_create_seeded");
+        else pl_check(hbmpc_pipe_fixedprep_create(fr, gl, n, t, nb, ni, lk_bits, stream, &h), fr, "hbmpc_pipe_fixedprep_create");
         return h;
     }
 };

@@ -468,6 +468,7 @@ extern "C" ShareErrorCode hbmpc_pipe_finish(hbmpc_pipe* pipe) {
 extern "C" ShareErrorCode hbmpc_pipe_capture(hbmpc_pipe* pipe) {
     if (!pipe || !pipe->stream) return InvalidInput;  // capture needs an explicit stream
     return guarded([&] {
+        pipe->before_capture();
         const bool was_checked = pipe->checked;
         pipe->checked = false;  // a captured run only enqueues
         struct Restore {

@@ -45,13 +45,18 @@ struct FixedPrep : hbmpc_pipe {
     unsigned char *st_t = nullptr, *st_2t = nullptr;
     size_t cur_bits = 0, cur_ints = 0;
     bool filled = false;
+    // seeded (hbmpc_pipe_fixedprep_create_seeded): both RISS parts are seeded handles; this handle's own `seeds` and index go to both
+    // before they run (PRandBit draws in domain 0, PRandInt in domain 1), and the index then advances past the longer of the two ranges
+    const bool seeded;
+    unsigned char* seeds = nullptr;
+    uint64_t index = 0;
 
     ~FixedPrep() override {
         (void)hbmpc_stream_sync(ctx, stream);
         hbmpc_graph_destroy(graph), graph = nullptr;  // before the stream it was recorded on
     }
-    FixedPrep(hbmpc_ctx* gl, hbmpc_ctx* fr_, size_t n_, size_t t_, size_t nbit_, size_t nint_, size_t lk, void* s)
-        : hbmpc_pipe(gl, s), fr(fr_), n(n_), t(t_), nbit(nbit_), nint(nint_) {
+    FixedPrep(hbmpc_ctx* gl, hbmpc_ctx* fr_, size_t n_, size_t t_, size_t nbit_, size_t nint_, size_t lk, void* s, bool seeded_)
+        : hbmpc_pipe(gl, s), fr(fr_), n(n_), t(t_), nbit(nbit_), nint(nint_), seeded(seeded_) {
         if (hbmpc_field_of(fr) != Bls12_381Fr || hbmpc_field_of(gl) != Goldilocks64) throw PipeError{TypeMismatch};
         if ((nbit == 0 && nint == 0) || n <= 2 * t) throw PipeError{InvalidInput};
         if (!stream) {  // the two contexts' own streams differ: without a caller's stream every part works on one of the handle's
@@ -67,11 +72,11 @@ struct FixedPrep : hbmpc_pipe {
             PL(hbmpc_pipe_randousha_create(gl, n, t, K2, stream, &rd.p));
             PL(hbmpc_pipe_triplegen_create(gl, n, t, T, stream, &tg.p));
             PL(hbmpc_pipe_randbit_create(gl, n, t, R, stream, &rb.p));
-            PL(hbmpc_pipe_prandbit_create(fr, gl, n, t, R, lk, 0, stream, &pb.p));
+            PL((seeded ? hbmpc_pipe_prandbit_create_seeded : hbmpc_pipe_prandbit_create)(fr, gl, n, t, R, lk, 0, stream, &pb.p));
             calls = K1 < ((size_t)1 << 19) && n * n * K1 * 8 < ((size_t)1 << 32);  // K2 <= K1
             if (calls) {
                 const size_t v2 = n - t - 1, w1 = 2 * n * n * K1 + (2 * t > t + 1 ? 2 * t : t + 1) * K1, w2 = 2 * n * n * K2 + v2 * n * K2;
-                arena((n * 2 * t * K1 + w1 + 2 * n * v2 * K2 + w2 + 2 * v2 * K2) * 8 + 2 * 4 * v2 * K2 + (1 << 13));
+                arena((n * 2 * t * K1 + w1 + 2 * n * v2 * K2 + w2 + 2 * v2 * K2) * 8 + 2 * 4 * v2 * K2 + (1 << 13) + (seeded ? n * 32 : 0));
                 yv = (uint64_t*)take(nullptr, n * 2 * t * K1), ws1 = (uint64_t*)take(nullptr, w1);
                 yv_t = (uint64_t*)take(nullptr, n * v2 * K2), yv_2t = (uint64_t*)take(nullptr, n * v2 * K2), ws2 = (uint64_t*)take(nullptr, w2);
                 sel_t = (uint64_t*)take(nullptr, v2 * K2), sel_2t = (uint64_t*)take(nullptr, v2 * K2);
@@ -93,9 +98,13 @@ struct FixedPrep : hbmpc_pipe {
             summ = reinterpret_cast<hbmpc_recover_summary*>(pb.buf("summary"));
         }
         if (nint) {
-            PL(hbmpc_pipe_prandint_create(fr, n, t, nint, lk, stream, &pi.p));
+            PL((seeded ? hbmpc_pipe_prandint_create_seeded : hbmpc_pipe_prandint_create)(fr, n, t, nint, lk, stream, &pi.p));
             r_int = pi.buf("r_p");
             buffers["r_int"] = Buffer{r_int, n * nint, 32};
+        }
+        if (seeded) {
+            if (!base) arena(n * 32 + 256);
+            seeds = take_typed("seeds", n * 32, 1);
         }
     }
     hbmpc_pipe* part(const std::string& name) override {
@@ -132,11 +141,28 @@ struct FixedPrep : hbmpc_pipe {
             take_cut(cut_triples);  // the first R triples (mod.rs:2022-2026); T - R stay in TripleGen's buffers
             PL(hbmpc_pipe_run(rb.p));
             take_cut(cut_bits);
+            seed_part(pb);
             PL(hbmpc_pipe_run(pb.p));
         }
-        if (nint) PL(hbmpc_pipe_run(pi.p));
+        if (nint) {
+            seed_part(pi);
+            PL(hbmpc_pipe_run(pi.p));
+        }
+        if (seeded) index += R > nint ? R : nint;
         replayed();
         if (checked) check();
+    }
+    void seed_part(const Part& part) {
+        if (!seeded) return;
+        PL(hbmpc_memcpy_d2d(fr, part.buf("seeds"), seeds, n * 32, stream));
+        PL(hbmpc_pipe_set_stream_index(part.p, index));
+    }
+    void before_capture() override {
+        if (seeded) refuse_seeded_capture();
+    }
+    void set_stream_index(uint64_t i) override {
+        if (!seeded) throw PipeError{InvalidInput};
+        index = i;
     }
     void run() override { rest(true); }
     void replayed() override { cur_bits = cur_ints = 0, filled = true; }
@@ -196,7 +222,13 @@ extern "C" ShareErrorCode hbmpc_pipe_fixedprep_create(hbmpc_ctx* ctx_fr, hbmpc_c
                                                       size_t lk_bits, void* stream, hbmpc_pipe** pipe_out) {
     if (pipe_out) *pipe_out = nullptr;
     if (!ctx_fr) return InvalidInput;
-    return create<FixedPrep>(ctx_gl, pipe_out, ctx_fr, n, t, n_prandbit, n_prandint, lk_bits, stream);
+    return create<FixedPrep>(ctx_gl, pipe_out, ctx_fr, n, t, n_prandbit, n_prandint, lk_bits, stream, false);
+}
+extern "C" ShareErrorCode hbmpc_pipe_fixedprep_create_seeded(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl, size_t n, size_t t, size_t n_prandbit,
+                                                             size_t n_prandint, size_t lk_bits, void* stream, hbmpc_pipe** pipe_out) {
+    if (pipe_out) *pipe_out = nullptr;
+    if (!ctx_fr) return InvalidInput;
+    return create<FixedPrep>(ctx_gl, pipe_out, ctx_fr, n, t, n_prandbit, n_prandint, lk_bits, stream, true);
 }
 extern "C" ShareErrorCode hbmpc_pipe_fixedprep_take(hbmpc_pipe* prep, size_t m, size_t N, void* rbits_dst, void* rint_dst) {
     FixedPrep* const p = dynamic_cast<FixedPrep*>(prep);

@@ -42,11 +42,10 @@ ShareErrorCode prand_fr_args(hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t tn, P
 
 // The eight launches: today's sequence (pipelines.py:PRandBit).  The open is BatchRecon of degree t from senders 0 .. S - 1: with
 // S = 2t + 1 a decode with no OEC round, a failed chunk final and opened to zero (as randbit_launches); a larger S takes the decodes' OEC path.
-ShareErrorCode prandbit_launches(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl, const PRandBitCall& c, size_t tn, size_t S, void* s) {
+// prandbit_tail: the seven after the fold, shared with the seeded call (capi_riss_seeded.inc), whose fold draws the contributions itself.
+ShareErrorCode prandbit_tail(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl, const PRandBitCall& c, size_t S, void* s) {
     const size_t n = c.n, t = c.t, B = c.B, G = B / (t + 1);
-    ShareErrorCode rc = hbmpc_dev_riss_fold(ctx_fr, c.contrib, n, tn, B, c.lk_bits, c.sums, c.bad, s);
-    if (rc != ShareSuccess) return rc;
-    rc = riss_convert_any(ctx_fr, c.sums, n, t, B, nullptr, n, 0, c.r_p, c.r_2, s);
+    ShareErrorCode rc = riss_convert_any(ctx_fr, c.sums, n, t, B, nullptr, n, 0, c.r_p, c.r_2, s);
     if (rc != ShareSuccess) return rc;
     rc = riss_convert_any(ctx_gl, c.sums, n, t, B, nullptr, n, 0, c.r_q, nullptr, s);
     if (rc != ShareSuccess) return rc;
@@ -62,6 +61,14 @@ ShareErrorCode prandbit_launches(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl, const PRa
                                     .summary = c.sm, .stream = s});
     if (rc != ShareSuccess) return rc;
     return hbmpc_dev_prandbit_finalize_parties(ctx_fr, c.opened, c.r_p, c.r_2, B, n, c.b_p, c.b_2, s);
+}
+ShareErrorCode prandbit_launches(hbmpc_ctx* ctx_fr, hbmpc_ctx* ctx_gl, const PRandBitCall& c, size_t tn, size_t S, void* s) {
+    const ShareErrorCode rc = hbmpc_dev_riss_fold(ctx_fr, c.contrib, c.n, tn, c.B, c.lk_bits, c.sums, c.bad, s);
+    return rc != ShareSuccess ? rc : prandbit_tail(ctx_fr, ctx_gl, c, S, s);
+}
+// PRandInt after the fold: the conversion over Fr
+ShareErrorCode prandint_tail(hbmpc_ctx* ctx_fr, size_t n, size_t t, size_t B, const uint64_t* sums, U256* r_p, void* s) {
+    return riss_convert_any(ctx_fr, sums, n, t, B, nullptr, n, 0, r_p, nullptr, s);
 }
 
 }  // namespace
@@ -146,5 +153,5 @@ extern "C" ShareErrorCode hbmpc_dev_prandint_parties(hbmpc_ctx* ctx_fr, const ui
     }
     rc = hbmpc_dev_riss_fold(ctx_fr, contrib, n, tn, B, lk_bits, sums, bad, s);
     if (rc != ShareSuccess) return rc;
-    return riss_convert_any(ctx_fr, sums, n, t, B, nullptr, n, 0, r_p, nullptr, s);
+    return prandint_tail(ctx_fr, n, t, B, sums, r_p, s);
 }

@@ -128,6 +128,9 @@ struct hbmpc_ctx {
 // the calling thread's last failure message (hbmpc_last_error): thread-local, so concurrent callers of one
 // context never write the same string
 static thread_local std::string g_err;
+namespace hbmpc_pipes {
+void set_last_error(const char* msg) { g_err = msg; }  // for a handle's own refusals (pipe_internal.hpp)
+}
 // > 0 while the calling thread is between hbmpc_graph_begin_capture and _end_capture (capture mode is thread-local):
 // tables and scratch it looks up are then pinned for the graph's lifetime, and nothing may be allocated
 static thread_local int g_capturing = 0;
@@ -2366,4 +2369,5 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
 #include "capi_batchrecon.inc"
 #include "capi_randbit.inc"
 #include "capi_prandbit.inc"
+#include "capi_riss_seeded.inc"
 #include "capi_producers.inc"

@@ -230,6 +230,12 @@ void launch_riss_convert(int impl, bool wide, const uint64_t* r, size_t B, unsig
                          uint32_t* out, uint8_t* out2, hipStream_t s);
 void launch_prandbit_finalize(int impl, const uint64_t* v, const uint32_t* r_p, const uint8_t* r_2, size_t N, unsigned parties, uint32_t* bp,
                               uint8_t* b2, hipStream_t s);  // Fr only
+// seeded RISS dealing (tu_riss_sample.hip, kernels_riss_sample.hpp; contract "hbmpc-riss-chacha20-v1"): one sender's out [Tn][B], or
+// seeds [n][8] words in device memory -> sums [Tn][B] of all n senders.  The grid of launch_riss_fold; bound = 2^lk_bits
+void launch_riss_sample(const uint32_t seed[8], uint32_t domain, size_t Tn, size_t B, uint64_t first_index, uint64_t bound, uint64_t* out,
+                        hipStream_t s);
+void launch_riss_sample_fold(const uint32_t* seeds, unsigned n, uint32_t domain, size_t Tn, size_t B, uint64_t first_index, uint64_t bound,
+                             uint64_t* sums, hipStream_t s);
 // PRandBit (bit) / PRandInt for all parties, a workgroup per chunk of t + 1 elements (kernels_prandbit_wg.hpp): the Fr side over U29
 // only (Goldilocks is the second field inside the same kernel).
 // false: the layout does not fit a workgroup's LDS or the LDS attribute could not be set; dry_run: only say which

@@ -105,6 +105,15 @@ struct Buffer {
 // k0, count} = batch elements [k0, k0 + count) of party p to dst + p * stride (elements)
 using Slice = hbmpc_list_slice;
 
+// the one thing a handle takes from the library that the public header does not offer: the calling thread's hbmpc_last_error text, for
+// a refusal that is the handle's own (defined beside that text, hbmpc_capi.hip)
+void set_last_error(const char* msg);
+// a seeded RISS handle refuses hbmpc_pipe_capture: every replay of the recording would draw the same stream positions again
+[[noreturn]] inline void refuse_seeded_capture() {
+    set_last_error("a seeded handle cannot be captured: a replayed graph would reuse the same stream positions");
+    throw PipeError{InvalidInput};
+}
+
 }  // namespace hbmpc_pipes
 using namespace hbmpc_pipes;
 
@@ -154,6 +163,8 @@ struct hbmpc_pipe {
     virtual void finish() { throw PipeError{InvalidInput}; }
     virtual hbmpc_pipe* part(const std::string&) { return nullptr; }
     virtual void replayed() {}  // hbmpc_pipe_replay has enqueued the recording: host-side state that run() resets (fixedprep's cursors)
+    virtual void before_capture() {}  // hbmpc_pipe_capture, before anything runs: a handle that cannot be recorded throws (the seeded RISS handles)
+    virtual void set_stream_index(uint64_t) { throw PipeError{InvalidInput}; }  // hbmpc_pipe_set_stream_index: the seeded RISS handles
     virtual void verdict(uint32_t out[2]) {
         if (!bad) throw PipeError{InvalidInput};
         PL(hbmpc_memcpy_d2h(ctx, out, bad, 8, stream));

@@ -792,6 +792,46 @@ class Engine:
         return self.L.hbmpc_dev_prandint_parties(self.ctx, C.c_void_p(contrib_d), *(C.c_size_t(v) for v in (n, t, B, lk_bits)),
                                                  *(C.c_void_p(p) for p in (sums_d, bad_d, rp_d)), C.c_void_p(stream))
 
+    # ---- seeded RISS dealing: contract "hbmpc-riss-chacha20-v1" (include/hbmpc_hip.h, csrc/kernels_riss_sample.hpp) ----
+    @staticmethod
+    def _seed(seed):
+        return (C.c_uint8 * 32).from_buffer_copy(bytes(seed))
+
+    def dev_riss_sample(self, seed, n, t, domain, B, first_index, lk_bits, out_d, stream=0):
+        """one sender's contributions from its 32-byte seed -> out [C(n,t)][B] u64 (device pointer); returns the ShareErrorCode"""
+        return self.L.hbmpc_dev_riss_sample(self.ctx, None if seed is None else self._seed(seed), C.c_size_t(n), C.c_size_t(t), C.c_size_t(domain),
+                                            C.c_size_t(B), C.c_uint64(first_index), C.c_size_t(lk_bits), C.c_void_p(out_d), C.c_void_p(stream))
+
+    def riss_sample(self, seed, n, t, domain, B, first_index, lk_bits):
+        """host-pointer form -> (rc, out [C(n,t)][B] uint64)"""
+        rc, sets = riss_tsets(n, t)
+        out = np.zeros((len(sets) if rc == 0 else 0, B), dtype=np.uint64)
+        rc = self.L.hbmpc_riss_sample(self.ctx, self._seed(seed), C.c_size_t(n), C.c_size_t(t), C.c_size_t(domain), C.c_size_t(B),
+                                      C.c_uint64(first_index), C.c_size_t(lk_bits), _p(out))
+        return rc, out
+
+    def riss_sample_fold(self, seeds_d, n, t, domain, B, first_index, lk_bits, sums_d, stream=0):
+        """seeds [n][32] bytes (device pointer) -> sums [C(n,t)][B] u64 over all n senders, contrib never materialised; returns the
+        ShareErrorCode"""
+        return self.L.hbmpc_dev_riss_sample_fold(self.ctx, C.c_void_p(seeds_d), C.c_size_t(n), C.c_size_t(t), C.c_size_t(domain), C.c_size_t(B),
+                                                 C.c_uint64(first_index), C.c_size_t(lk_bits), C.c_void_p(sums_d), C.c_void_p(stream))
+
+    def prandbit_parties_seeded(self, eng_gl, seeds_d, first_index, bq_d, n, t, B, lk_bits, sums_d, bad_d, rp_d, r2_d, rq_d, rb_d, y_d, z_d, opened_d,
+                                bp_d, b2_d, rstatus_d, summary_first_d=0, summary_d=0, open_senders=0, stream=0):
+        """prandbit_parties with contrib replaced by (seeds [n][32] bytes on the device, first_index): the contributions are drawn in
+        domain 0 and folded in registers; always the separate launches; returns the ShareErrorCode"""
+        return self.L.hbmpc_dev_prandbit_parties_seeded(self.ctx, eng_gl.ctx if eng_gl is not None else None, C.c_void_p(seeds_d),
+                                                        C.c_uint64(first_index), C.c_void_p(bq_d),
+                                                        *(C.c_size_t(v) for v in (n, t, B, lk_bits, open_senders)),
+                                                        *(C.c_void_p(p) for p in (sums_d, bad_d, rp_d, r2_d, rq_d, rb_d, y_d, z_d, opened_d, bp_d, b2_d,
+                                                                                  rstatus_d, summary_first_d, summary_d)), C.c_void_p(stream))
+
+    def prandint_parties_seeded(self, seeds_d, first_index, n, t, B, lk_bits, sums_d, bad_d, rp_d, stream=0):
+        """prandint_parties with contrib replaced by (seeds, first_index), drawn in domain 1; returns the ShareErrorCode"""
+        return self.L.hbmpc_dev_prandint_parties_seeded(self.ctx, C.c_void_p(seeds_d), C.c_uint64(first_index),
+                                                        *(C.c_size_t(v) for v in (n, t, B, lk_bits)),
+                                                        *(C.c_void_p(p) for p in (sums_d, bad_d, rp_d)), C.c_void_p(stream))
+
     def set_fused_prandbit(self, max_chunks: int):
         """hbmpc_dev_prandbit_parties / _prandint_parties are one launch up to this many chunks of t + 1 elements (0: always the
         separate launches); read from the Fr engine"""

@@ -439,6 +439,10 @@ class _RissPipe(_Pipe):
     _EB = {"contrib": 8, "b_q": 8, "sums": 8, "bad": 1, "r_p": 32, "r_2": 1, "r_q": 8, "rb": 8, "Y": 8, "Z": 8, "opened": 8, "b_p": 32, "b_2": 1,
            "rstatus": 1, "summary_first": 1, "summary": 1}
 
+    def _seeded_names(self):
+        """a seeded handle's own table of buffers: seeds ([n][32] bytes) where contrib was"""
+        self._EB = {k: v for k, v in self._EB.items() if k != "contrib"} | {"seeds": 1}
+
     def upload_named(self, name, arr):
         arr = np.ascontiguousarray(arr)
         self._rc(self.eng.L.hbmpc_pipe_upload(self.h, name.encode(), arr.ctypes.data_as(C.c_void_p), C.c_size_t(arr.nbytes // self._EB[name])),
@@ -451,20 +455,34 @@ class _RissPipe(_Pipe):
         self._rc(self.eng.L.hbmpc_pipe_download(self.h, name.encode(), out.ctypes.data_as(C.c_void_p), C.c_size_t(count)), f"download {name!r}")
         return out if shape is None else out.reshape(shape)
 
+    def set_stream_index(self, index):
+        """seeded handles (hbmpc_pipe_set_stream_index): the next run() draws at [index, index + B) and then advances by B"""
+        self._rc(self.eng.L.hbmpc_pipe_set_stream_index(self.h, C.c_uint64(index)), "set_stream_index")
+
+    def upload_seeds(self, seeds):
+        """seeded handles: one 32-byte seed per sender"""
+        seeds = np.frombuffer(b"".join(bytes(s) for s in seeds), dtype=np.uint8)
+        assert seeds.size == 32 * self.n
+        self.upload_named("seeds", seeds)
+
 
 class PRandIntPipe(_RissPipe):
     """PRandInt for all n parties as one handle (hbmpc_pipe_prandint_create; prandbitd.rs:667-684, 311-356): contrib [n][C(n,t)][B] u64
     -> sums [C(n,t)][B], bad [n][C(n,t)] verdict bytes, r_p [n][B] the Fr shares.  Any B.  run() is one library call
     (hbmpc_dev_prandint_parties): ONE launch up to hbmpc_set_fused_prandbit chunks of t + 1 elements for the shapes whose tables fit a
-    workgroup's LDS, two launches otherwise."""
+    workgroup's LDS, two launches otherwise.  seeded=True (hbmpc_pipe_prandint_create_seeded): a buffer seeds [n][32] bytes and no
+    contrib; run() draws the contributions on the device at the handle's stream index (contract "hbmpc-riss-chacha20-v1", domain 1) and
+    advances it by B; capture() is refused."""
 
-    def __init__(self, eng_fr, n, t, B, lk_bits, stream=0, _handle=None):
-        self.n, self.t, self.B, self.lk_bits = n, t, B, lk_bits
+    def __init__(self, eng_fr, n, t, B, lk_bits, stream=0, _handle=None, seeded=False):
+        self.n, self.t, self.B, self.lk_bits, self.seeded = n, t, B, lk_bits, seeded
+        if seeded:
+            self._seeded_names()
         h = _handle or C.c_void_p()
-        rc = 0 if _handle else eng_fr.L.hbmpc_pipe_prandint_create(eng_fr.ctx, *[C.c_size_t(v) for v in (n, t, B, lk_bits)], C.c_void_p(stream),
-                                                                   C.byref(h))
+        fn = "hbmpc_pipe_prandint_create_seeded" if seeded else "hbmpc_pipe_prandint_create"
+        rc = 0 if _handle else getattr(eng_fr.L, fn)(eng_fr.ctx, *[C.c_size_t(v) for v in (n, t, B, lk_bits)], C.c_void_p(stream), C.byref(h))
         if rc != 0:
-            raise RuntimeError(f"hbmpc_pipe_prandint_create{(n, t, B, lk_bits)} -> ShareErrorCode {rc}: {eng_fr.last_error()}")
+            raise RuntimeError(f"{fn}{(n, t, B, lk_bits)} -> ShareErrorCode {rc}: {eng_fr.last_error()}")
         super().__init__(eng_fr, h, stream)
 
 
@@ -474,18 +492,22 @@ class PRandBitPipe(_RissPipe):
     opened [B], b_p [n][B] Fr, b_2 [n][B] bytes, rstatus, summary_first, summary.  B a multiple of t + 1.  open_senders: how many parties'
     messages the open decodes from; default 2t + 1 (no OEC round: BatchRecon acts as soon as d + t + 1 values have arrived).  run() is one
     library call (hbmpc_dev_prandbit_parties): ONE launch up to hbmpc_set_fused_prandbit chunks when the open has exactly 2t + 1 senders
-    and the tables fit a workgroup's LDS ((4,1) .. (12,3)), eight launches otherwise."""
+    and the tables fit a workgroup's LDS ((4,1) .. (12,3)), eight launches otherwise.  seeded=True (hbmpc_pipe_prandbit_create_seeded):
+    seeds [n][32] bytes instead of contrib, drawn in domain 0 at the handle's stream index, always the separate launches; capture() is
+    refused."""
 
-    def __init__(self, eng_gl, eng_fr, n, t, B, lk_bits, stream=0, open_senders=None, _handle=None):
-        self.n, self.t, self.B, self.lk_bits, self.G = n, t, B, lk_bits, B // (t + 1)
+    def __init__(self, eng_gl, eng_fr, n, t, B, lk_bits, stream=0, open_senders=None, _handle=None, seeded=False):
+        self.n, self.t, self.B, self.lk_bits, self.G, self.seeded = n, t, B, lk_bits, B // (t + 1), seeded
         self.open_senders = 2 * t + 1 if open_senders is None else open_senders
         self.fr = eng_fr
+        if seeded:
+            self._seeded_names()
         h = _handle or C.c_void_p()
-        rc = 0 if _handle else eng_fr.L.hbmpc_pipe_prandbit_create(eng_fr.ctx, eng_gl.ctx,
-                                                                   *[C.c_size_t(v) for v in (n, t, B, lk_bits, self.open_senders)],
-                                                                   C.c_void_p(stream), C.byref(h))
+        fn = "hbmpc_pipe_prandbit_create_seeded" if seeded else "hbmpc_pipe_prandbit_create"
+        rc = 0 if _handle else getattr(eng_fr.L, fn)(eng_fr.ctx, eng_gl.ctx, *[C.c_size_t(v) for v in (n, t, B, lk_bits, self.open_senders)],
+                                                     C.c_void_p(stream), C.byref(h))
         if rc != 0:
-            raise RuntimeError(f"hbmpc_pipe_prandbit_create{(n, t, B, lk_bits, self.open_senders)} -> ShareErrorCode {rc}: {eng_fr.last_error()}")
+            raise RuntimeError(f"{fn}{(n, t, B, lk_bits, self.open_senders)} -> ShareErrorCode {rc}: {eng_fr.last_error()}")
         super().__init__(eng_gl, h, stream)  # the handle's own context is the Goldilocks one (the open's decode counters are its)
 
     def open_summary(self):
@@ -500,7 +522,8 @@ class FixedPrep(_RissPipe):
     2t + 1, K1 = ceil((R + 2T) / (n - 2t)) RanSha columns per dealer, K2 = ceil(T / (t + 1)) RanDouSha columns.  Parts (borrowed): rs, rd,
     tg, rb over Goldilocks, pb (PRandBitPipe), pi (PRandIntPipe); None where that half is absent.  Buffers r_bits [n][R] U256, r_bits2
     [n][R] bytes, r_int [n][n_prandint] U256.  deal() / finish() are the halves of run(); take(consumer, N) moves N elements' worth from
-    the front of the pools into an FpMul / TruncPr handle's rbits / rint."""
+    the front of the pools into an FpMul / TruncPr handle's rbits / rint.  seeded=True (hbmpc_pipe_fixedprep_create_seeded): pb and pi are
+    seeded handles, fed from this handle's own seeds [n][32] bytes and stream index before each run; capture() is refused."""
     _EB = {"r_bits": 32, "r_bits2": 1, "r_int": 32}
 
     @staticmethod
@@ -510,13 +533,17 @@ class FixedPrep(_RissPipe):
         T = -(-R // (2 * t + 1)) * (2 * t + 1)
         return R, T, -(-(R + 2 * T) // (n - 2 * t)), -(-T // (t + 1))
 
-    def __init__(self, eng_gl, eng_fr, n, t, n_prandbit, n_prandint, lk_bits, stream=0):
+    def __init__(self, eng_gl, eng_fr, n, t, n_prandbit, n_prandint, lk_bits, stream=0, seeded=False):
         self.n, self.t, self.n_prandbit, self.n_prandint, self.lk_bits, self.fr = n, t, n_prandbit, n_prandint, lk_bits, eng_fr
+        self.seeded = seeded
+        if seeded:
+            self._seeded_names()
         h = C.c_void_p()
-        rc = eng_fr.L.hbmpc_pipe_fixedprep_create(eng_fr.ctx, eng_gl.ctx, *[C.c_size_t(v) for v in (n, t, n_prandbit, n_prandint, lk_bits)],
-                                                  C.c_void_p(stream), C.byref(h))
+        fn = "hbmpc_pipe_fixedprep_create_seeded" if seeded else "hbmpc_pipe_fixedprep_create"
+        rc = getattr(eng_fr.L, fn)(eng_fr.ctx, eng_gl.ctx, *[C.c_size_t(v) for v in (n, t, n_prandbit, n_prandint, lk_bits)], C.c_void_p(stream),
+                                   C.byref(h))
         if rc != 0:
-            raise RuntimeError(f"hbmpc_pipe_fixedprep_create{(n, t, n_prandbit, n_prandint, lk_bits)} -> ShareErrorCode {rc}: {eng_fr.last_error()}")
+            raise RuntimeError(f"{fn}{(n, t, n_prandbit, n_prandint, lk_bits)} -> ShareErrorCode {rc}: {eng_fr.last_error()}")
         super().__init__(eng_gl, h, stream)
         self.rs = self.rd = self.tg = self.rb = self.pb = self.pi = None
         if n_prandbit:
@@ -525,9 +552,9 @@ class FixedPrep(_RissPipe):
             self.rd = RanDouSha(eng_gl, n, t, self.K2, stream, _handle=self._part("randousha"))
             self.tg = TripleGen(eng_gl, n, t, self.T, stream, _handle=self._part("triplegen"))
             self.rb = RandBit(eng_gl, n, t, self.R, stream, _handle=self._part("randbit"))
-            self.pb = PRandBitPipe(eng_gl, eng_fr, n, t, self.R, lk_bits, stream, _handle=self._part("prandbit"))
+            self.pb = PRandBitPipe(eng_gl, eng_fr, n, t, self.R, lk_bits, stream, _handle=self._part("prandbit"), seeded=seeded)
         if n_prandint:
-            self.pi = PRandIntPipe(eng_fr, n, t, n_prandint, lk_bits, stream, _handle=self._part("prandint"))
+            self.pi = PRandIntPipe(eng_fr, n, t, n_prandint, lk_bits, stream, _handle=self._part("prandint"), seeded=seeded)
         for part in (self.rs, self.rd, self.tg, self.rb, self.pb, self.pi):
             if part is not None:
                 part._own = False  # borrowed: destroyed with this handle

@@ -414,6 +414,64 @@ impl GpuShares {
         let rc = unsafe { sys::hbmpc_pipe_fixedprep_create(self.ctx, gl.ctx, n, t, n_prandbit, n_prandint, l_plus_k, stream, &mut p) };
         self.wrap(rc, p, n)
     }
+    // ---- seeded RISS dealing (contract "hbmpc-riss-chacha20-v1", include/hbmpc_hip.h): ONE seed per sender, and a (seed, domain, index)
+    // range is never reused -- take `first_index` from a counter that only grows, as the seeded pipelines do
+    /// this node's own contributions from its seed: `out` [sets][batch], row T for the parties outside T.  `Err(true)`:
+    /// `PRandError::SurpassedFieldCapacity`
+    #[allow(clippy::too_many_arguments)]
+    pub fn riss_sample_dev(&self, seed: &[u8; 32], n: usize, t: usize, domain: usize, batch: usize, first_index: u64, l_plus_k: usize, out: *mut u64,
+                           stream: *mut core::ffi::c_void) -> Result<(), bool> {
+        match unsafe { sys::hbmpc_dev_riss_sample(self.ctx, seed.as_ptr(), n, t, domain, batch, first_index, l_plus_k, out, stream) } {
+            sys::ShareSuccess => Ok(()),
+            sys::HBMPC_FIELD_CAPACITY => Err(true),
+            _ => Err(false),
+        }
+    }
+    /// the host-pointer form: -> [sets][batch]
+    pub fn riss_sample(&self, seed: &[u8; 32], n: usize, t: usize, domain: usize, batch: usize, first_index: u64, l_plus_k: usize) -> Result<Vec<u64>, bool> {
+        let sets = Self::riss_tsets(n, t).ok_or(false)?.len();
+        let mut out = vec![0u64; sets * batch];
+        match unsafe { sys::hbmpc_riss_sample(self.ctx, seed.as_ptr(), n, t, domain, batch, first_index, l_plus_k, out.as_mut_ptr()) } {
+            sys::ShareSuccess => Ok(out),
+            sys::HBMPC_FIELD_CAPACITY => Err(true),
+            _ => Err(false),
+        }
+    }
+    /// all n senders' values drawn and folded in registers: `seeds` [n][8] u32 on the device -> `sums` [sets][batch]
+    #[allow(clippy::too_many_arguments)]
+    pub fn riss_sample_fold_dev(&self, seeds: *const u32, n: usize, t: usize, domain: usize, batch: usize, first_index: u64, l_plus_k: usize,
+                                sums: *mut u64, stream: *mut core::ffi::c_void) -> Result<(), bool> {
+        match unsafe { sys::hbmpc_dev_riss_sample_fold(self.ctx, seeds, n, t, domain, batch, first_index, l_plus_k, sums, stream) } {
+            sys::ShareSuccess => Ok(()),
+            sys::HBMPC_FIELD_CAPACITY => Err(true),
+            _ => Err(false),
+        }
+    }
+    /// PRandInt for all n parties from the senders' seeds (domain 1): `sums`, `bad` (zeros), `r_p` as `hbmpc_dev_prandint_parties` writes them
+    #[allow(clippy::too_many_arguments)]
+    pub fn prandint_parties_seeded_dev(&self, seeds: *const u32, first_index: u64, n: usize, t: usize, batch: usize, l_plus_k: usize, sums: *mut u64,
+                                       bad: *mut u8, r_p: *mut sys::U256, stream: *mut core::ffi::c_void) -> Result<(), InterpolateError> {
+        let rc = unsafe { sys::hbmpc_dev_prandint_parties_seeded(self.ctx, seeds, first_index, n, t, batch, l_plus_k, sums, bad, r_p, stream) };
+        self.check(rc, n)
+    }
+    /// the seeded pipelines: a buffer `seeds` ([n][32] bytes, `upload_bytes`) and no `contrib`; `set_stream_index`; `capture` is refused
+    pub fn pipe_prandbit_seeded<'a>(&'a self, gl: &'a GpuShares, n: usize, t: usize, bits: usize, l_plus_k: usize,
+                                    stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'a>, InterpolateError> {
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_prandbit_create_seeded(self.ctx, gl.ctx, n, t, bits, l_plus_k, 0, stream, &mut p) };
+        self.wrap(rc, p, n)
+    }
+    pub fn pipe_prandint_seeded(&self, n: usize, t: usize, batch: usize, l_plus_k: usize, stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'_>, InterpolateError> {
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_prandint_create_seeded(self.ctx, n, t, batch, l_plus_k, stream, &mut p) };
+        self.wrap(rc, p, n)
+    }
+    pub fn pipe_fixedprep_seeded<'a>(&'a self, gl: &'a GpuShares, n: usize, t: usize, n_prandbit: usize, n_prandint: usize, l_plus_k: usize,
+                                     stream: *mut core::ffi::c_void) -> Result<GpuPipeline<'a>, InterpolateError> {
+        let mut p = std::ptr::null_mut();
+        let rc = unsafe { sys::hbmpc_pipe_fixedprep_create_seeded(self.ctx, gl.ctx, n, t, n_prandbit, n_prandint, l_plus_k, stream, &mut p) };
+        self.wrap(rc, p, n)
+    }
     /// hbmpc_dev_take_rows: slices of `[party][len]` pools, regrouped, in one launch (at most 8 slices).  Safety: every pointer of every
     /// slice is a device buffer that holds `rows` rows at its stride
     pub unsafe fn take_rows(&self, slices: &[sys::TakeSlice], rows: usize, stream: *mut core::ffi::c_void) -> Result<(), InterpolateError> {
@@ -493,6 +551,13 @@ impl<'a> GpuPipeline<'a> {
         self.gpu.check(rc, 0)?;
         Ok(v)
     }
+    /// the seeded handles' `seeds`: n seeds of 32 bytes, one per sender
+    pub fn upload_bytes(&self, name: &str, bytes: &[u8]) -> Result<(), InterpolateError> {
+        let rc = unsafe { sys::hbmpc_pipe_upload(self.pipe, Self::name(name).as_ptr(), bytes.as_ptr() as *const core::ffi::c_void, bytes.len()) };
+        self.gpu.check(rc, 0)?;
+        let rc = unsafe { sys::hbmpc_pipe_sync(self.pipe) };  // the copy reads `bytes`
+        self.gpu.check(rc, 0)
+    }
     /// enqueue the whole pipeline on its stream
     pub fn run(&self) -> Result<(), InterpolateError> {
         let rc = unsafe { sys::hbmpc_pipe_set_checked(self.pipe, 0) };
@@ -528,6 +593,11 @@ impl<'a> GpuPipeline<'a> {
     /// Safety: the destinations are device buffers of those sizes
     pub unsafe fn take(&self, m: usize, pairs: usize, rbits: *mut sys::U256, rint: *mut sys::U256) -> Result<(), InterpolateError> {
         let rc = sys::hbmpc_pipe_fixedprep_take(self.pipe, m, pairs, rbits as *mut core::ffi::c_void, rint as *mut core::ffi::c_void);
+        self.gpu.check(rc, 0)
+    }
+    /// a seeded pipeline: the stream position of the next `run`, which then advances it by its batch
+    pub fn set_stream_index(&self, index: u64) -> Result<(), InterpolateError> {
+        let rc = unsafe { sys::hbmpc_pipe_set_stream_index(self.pipe, index) };
         self.gpu.check(rc, 0)
     }
     /// (bits, integers) left in a FixedPrep pipeline's pools
