@@ -416,6 +416,46 @@ ShareErrorCode hbmpc_dev_compute_shares_seeded(hbmpc_ctx* ctx, const uint8_t see
 ShareErrorCode hbmpc_compute_shares_seeded(hbmpc_ctx* ctx, const uint8_t seed[32], const U256* secrets, size_t B,
                                            uint64_t first_index, size_t n, size_t d, U256* shares_out);
 
+/* ==== Shamirshare: the integer-point scheme (common/share/shamir.rs:13-126) ==================
+ * The third share family of the reference, and one its C ABI exports (ffi/c_bindings/share/mod.rs:288-385); the field half of
+ * FeldmanShamirShare (feldman.rs:164-265) and of every open of avss_mpc.  A share sits at the field element F::from(id as u64) --
+ * the id reduced mod p -- not at a root of unity: `points` below are such ids (usually 1..n), NOT indices into the evaluation
+ * domain, and the two kinds of call never share a table (the points [1,2,3] and the domain ids [1,2,3] are different point sets).
+ *
+ * compute_shares (shamir.rs:44-88) for B secrets: coeffs[B][d+1] chunk-major as for hbmpc_compute_shares, shares_out[m][B]
+ * point-major, shares_out[i][b] = sum_k coeffs[b][k] points[i]^k.  points[m] is a HOST array in the device form too (it selects the
+ * constant tables, like sender_ids).  Errors in the reference's order (:51-70): points == NULL InvalidInput; m < d+1
+ * InsufficientShares; an id = 0 mod p InvalidInput; duplicate ids, compared as INTEGERS, InvalidInput -- over Goldilocks {1, p+1}
+ * is accepted and yields two equal rows, as in the reference.  Then this library's: m, d <= 2^20.
+ * There is no seeded entry: hbmpc_[gl_]dev_fill_coeffs followed by hbmpc_[gl_]dev_shamir_compute_shares is the seeded form.
+ * Kernels (csrc/shamir_route.hpp): when every points[i]^d < 2^64 the weights are plain integers and an output is d+1 products by a
+ * 64-bit word with one reduction (csrc/kernels_shamir.hpp); other calls, and small batches, run the Horner kernels of the domain
+ * encode with the points as alpha.  Same results either way. */
+ShareErrorCode hbmpc_shamir_compute_shares(hbmpc_ctx* ctx, const U256* coeffs, size_t B, const uint64_t* points, size_t m, size_t d,
+                                           U256* shares_out);
+ShareErrorCode hbmpc_dev_shamir_compute_shares(hbmpc_ctx* ctx, const U256* coeffs_dev, size_t B, const uint64_t* points, size_t m,
+                                               size_t d, U256* shares_out_dev, void* stream);
+/* recover_secret (shamir.rs:90-125) for one polynomial: plain Lagrange through ALL S shares.  Errors in the reference's order: S == 0
+ * InvalidInput; duplicate integer ids InvalidInput; unequal degrees DegreeMismatch; S < degrees[0]+1 InsufficientShares; an id = 0
+ * mod p InvalidInput; two ids equal as field elements InvalidInput (common/mod.rs:141-144); interpolated degree > degrees[0]
+ * DegreeMismatch.  coeffs_out has room for S elements, *ncoeffs_out = the trimmed length, *secret_out = P(0).  For the zero
+ * polynomial the reference indexes result_poly[0] and panics; this returns ShareSuccess, length 0 and secret 0 (as
+ * hbmpc_nonrobust_recover_secret does). */
+ShareErrorCode hbmpc_shamir_recover_secret(hbmpc_ctx* ctx, const uint64_t* ids, const size_t* degrees, const U256* vals, size_t S,
+                                           U256* coeffs_out, size_t* ncoeffs_out, U256* secret_out);
+/* The batched open: the contracts of hbmpc_batch_interpolate, hbmpc_dev_batch_interpolate and hbmpc_dev_batch_interpolate_c0 (row_stride,
+ * coeffs_out[G][S] not trimmed, degree_out[G], c0_out[G]; S <= 255) with points[S] in place of domain ids and no n.  Errors: S == 0 or
+ * G == 0, duplicate integer ids, an id = 0 mod p, two ids equal as field elements: InvalidInput.  The caller compares degree_out with
+ * the share degree (shamir.rs:120-122), as for the RanDouSha verifier.  The decode kernels are those of hbmpc_dev_batch_interpolate,
+ * fed the inverse-Vandermonde table of the points. */
+ShareErrorCode hbmpc_shamir_batch_interpolate(hbmpc_ctx* ctx, const uint64_t* points, size_t S, const U256* evals, size_t G,
+                                              U256* coeffs_out, uint32_t* degree_out);
+ShareErrorCode hbmpc_dev_shamir_batch_interpolate(hbmpc_ctx* ctx, const uint64_t* points, size_t S, const U256* evals_dev, size_t row_stride,
+                                                  size_t G, U256* coeffs_out_dev, uint32_t* degree_out_dev, void* stream);
+ShareErrorCode hbmpc_dev_shamir_batch_interpolate_c0(hbmpc_ctx* ctx, const uint64_t* points, size_t S, const U256* evals_dev,
+                                                     size_t row_stride, size_t G, U256* tmp_coeffs_dev, U256* c0_out_dev,
+                                                     uint32_t* degree_out_dev, void* stream);
+
 /* ==== a4+a5: make_vandermonde + apply_vandermonde ===========================================
  * replaces common/share/mod.rs:31-76 as used by BatchReconNode::init_batch_reconstruct[_many]
  * (batch_recon.rs:114-115,157-165), RanSha (share_gen.rs:415-419) and RanDouSha
@@ -1103,6 +1143,22 @@ ShareErrorCode hbmpc_gl_gao_rs_decode(hbmpc_ctx* ctx, const uint64_t* received, 
 ShareErrorCode hbmpc_gl_nonrobust_recover_secret(hbmpc_ctx* ctx, const size_t* ids, const size_t* degrees,
                                                  const uint64_t* vals, size_t S, size_t n, uint64_t* coeffs_out,
                                                  size_t* ncoeffs_out, uint64_t* secret_out);
+/* the integer-point scheme over Goldilocks (hbmpc_shamir_* above): ids p, p+1, .. 2^64-1 are legal u64 ids whose field elements are
+ * id - p; an id = p is refused as zero, {1, p+1} is two shares at the same point for the encode and a refusal for the interpolation */
+ShareErrorCode hbmpc_gl_shamir_compute_shares(hbmpc_ctx* ctx, const uint64_t* coeffs, size_t B, const uint64_t* points, size_t m, size_t d,
+                                              uint64_t* shares_out);
+ShareErrorCode hbmpc_gl_dev_shamir_compute_shares(hbmpc_ctx* ctx, const uint64_t* coeffs_dev, size_t B, const uint64_t* points, size_t m,
+                                                  size_t d, uint64_t* shares_out_dev, void* stream);
+ShareErrorCode hbmpc_gl_shamir_recover_secret(hbmpc_ctx* ctx, const uint64_t* ids, const size_t* degrees, const uint64_t* vals, size_t S,
+                                              uint64_t* coeffs_out, size_t* ncoeffs_out, uint64_t* secret_out);
+ShareErrorCode hbmpc_gl_shamir_batch_interpolate(hbmpc_ctx* ctx, const uint64_t* points, size_t S, const uint64_t* evals, size_t G,
+                                                 uint64_t* coeffs_out, uint32_t* degree_out);
+ShareErrorCode hbmpc_gl_dev_shamir_batch_interpolate(hbmpc_ctx* ctx, const uint64_t* points, size_t S, const uint64_t* evals_dev,
+                                                     size_t row_stride, size_t G, uint64_t* coeffs_out_dev, uint32_t* degree_out_dev,
+                                                     void* stream);
+ShareErrorCode hbmpc_gl_dev_shamir_batch_interpolate_c0(hbmpc_ctx* ctx, const uint64_t* points, size_t S, const uint64_t* evals_dev,
+                                                        size_t row_stride, size_t G, uint64_t* tmp_coeffs_dev, uint64_t* c0_out_dev,
+                                                        uint32_t* degree_out_dev, void* stream);
 ShareErrorCode hbmpc_gl_fr_op(hbmpc_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, size_t N, uint64_t* out);
 ShareErrorCode hbmpc_gl_fr_op_scalar(hbmpc_ctx* ctx, int op, const uint64_t* a, const uint64_t* scalar, size_t N, uint64_t* out);
 ShareErrorCode hbmpc_gl_dev_fr_op_scalar(hbmpc_ctx* ctx, int op, const uint64_t* a_dev, const uint64_t* scalar_host, size_t N,
@@ -1408,6 +1464,12 @@ ShareErrorCode hbmpc_debug_mfma_table(hbmpc_ctx* ctx, const size_t* sorted_ids, 
                                       uint8_t* out, size_t cap, size_t* bytes_out);
 /* test aid: 1 = route every shape through the generic (runtime-shaped) kernels */
 ShareErrorCode hbmpc_set_force_generic(hbmpc_ctx* ctx, int on);
+/* test and sweep aid, either field: the route of hbmpc_[gl_]dev_shamir_compute_shares (csrc/shamir_route.hpp).  0 = the planner's rule,
+ * 1 = the small-weight kernel wherever it covers the call (every points[i]^d < 2^64), at every batch size, 2 = never.  Same results. */
+ShareErrorCode hbmpc_set_shamir_route(hbmpc_ctx* ctx, int route);
+/* test aid: the kernel that rule picks on this context for a call (1 = small-weight, 2 = a wave per secret, 3 = a lane per secret);
+ * the encode's checks apply */
+ShareErrorCode hbmpc_shamir_route(hbmpc_ctx* ctx, const uint64_t* points, size_t m, size_t d, size_t B, int* kernel_out);
 /* Secret hygiene.  The host-pointer calls stage their arguments through per-context pools (device buffers, pinned host
  * blocks) that are recycled between calls, so copies of polynomial coefficients (secrets) and shares stay there until
  * a later call overwrites them.  hbmpc_scrub_staging zeroes everything the pools hold at that moment (it drains the
@@ -1417,7 +1479,7 @@ ShareErrorCode hbmpc_set_force_generic(hbmpc_ctx* ctx, int on);
  * the caller's to clear. */
 ShareErrorCode hbmpc_scrub_staging(hbmpc_ctx* ctx);
 /* The device-table cache of a context (twiddles, Vandermonde rows, one Lagrange/verify table and one OEC/Gao table
- * per sender set) is bounded: at 512 tables everything not referenced by a captured graph is evicted (unlinked now,
+ * per sender set; a sender set of domain ids and a set of integer points are keyed apart) is bounded: at 512 tables everything not referenced by a captured graph is evicted (unlinked now,
  * freed at the next eviction, so a concurrent call that already looked a table up never loses it).
  * stats_out = {tables cached, of which pinned by graphs, evicted-but-not-yet-freed, evictions so far}. */
 ShareErrorCode hbmpc_cache_stats(hbmpc_ctx* ctx, size_t stats_out[4]);

@@ -7,6 +7,7 @@
 //   SecretSharingScheme: compute_shares / recover_secret          common/mod.rs:101-128
 //   RobustShare  = ShamirShare<Robust>                            honeybadger/robust_interpolate/robust_interpolate.rs:17-157
 //   NonRobustShare                                                common/share/shamir.rs:131-240
+//   Shamirshare (integer evaluation points F::from(id))           common/share/shamir.rs:13-126
 //   make_vandermonde / apply_vandermonde                          common/share/mod.rs:31-76
 //   batch_recover_secret                                          robust_interpolate.rs:284-443
 //   gao_rs_decode (private there, called by its unit tests)       robust_interpolate.rs:456-538
@@ -50,6 +51,7 @@ struct Result {
 
 struct Robust {};
 struct NonRobust {};
+struct Shamir {};  // the integer-point scheme: a share's id is its evaluation point F::from(id), not an index into the domain
 
 namespace detail {
 inline hbmpc_ctx* make_context(FieldKind kind) {
@@ -79,6 +81,8 @@ struct FrTraits {  // ark_bls12_381::Fr <-> U256 (ffi/c_bindings/mod.rs:37-49)
     static constexpr auto nonrobust_recover_secret = hbmpc_nonrobust_recover_secret;
     static constexpr auto gao_rs_decode = hbmpc_gao_rs_decode;
     static constexpr auto fr_op = hbmpc_fr_op;
+    static constexpr auto shamir_compute_shares = hbmpc_shamir_compute_shares;
+    static constexpr auto shamir_recover_secret = hbmpc_shamir_recover_secret;
 };
 struct GlTraits {  // GoldilocksField = Fp64 <-> u64 (common/math/goldilocks.rs:4-13)
     using repr = uint64_t;
@@ -97,6 +101,8 @@ struct GlTraits {  // GoldilocksField = Fp64 <-> u64 (common/math/goldilocks.rs:
     static constexpr auto nonrobust_recover_secret = hbmpc_gl_nonrobust_recover_secret;
     static constexpr auto gao_rs_decode = hbmpc_gl_gao_rs_decode;
     static constexpr auto fr_op = hbmpc_gl_fr_op;
+    static constexpr auto shamir_compute_shares = hbmpc_gl_shamir_compute_shares;
+    static constexpr auto shamir_recover_secret = hbmpc_gl_shamir_recover_secret;
 };
 
 template <class FT>
@@ -258,6 +264,41 @@ struct Scheme {
         }
     };
 
+    // Shamirshare (common/share/shamir.rs:13-126): shares at the field elements F::from(id), plain Lagrange recovery
+    struct Shamirshare : ShamirShare<Shamir> {
+        using ShamirShare<Shamir>::ShamirShare;
+        Shamirshare(const ShamirShare<Shamir>& s) : ShamirShare<Shamir>(s) {}
+        // SecretSharingScheme::compute_shares (shamir.rs:44-88): `n` is unused there too, `ids` is required (None: InvalidInput); the
+        // checks and their order are hbmpc_shamir_compute_shares'
+        static Result<std::vector<ShamirShare<Shamir>>> compute_shares(const F& secret, size_t /*n*/, size_t degree, const std::vector<size_t>* ids,
+                                                                       Rng& rng) {
+            using V = std::vector<ShamirShare<Shamir>>;
+            if (!ids) return Result<V>::err(InvalidInput);              // :51-54
+            if (ids->size() < degree + 1) return Result<V>::err(InsufficientShares);  // :57-59, before any draw
+            // the id checks (:62-70) come before DensePolynomial::rand in the reference: no draw is consumed by a refused call
+            std::vector<uint64_t> points(ids->begin(), ids->end());
+            std::vector<repr> probe(degree + 1, FT::from_u64(0)), out(points.size());
+            ShareErrorCode rc = FT::shamir_compute_shares(FT::context(), probe.data(), 0, points.data(), points.size(), degree, out.data());
+            if (rc != ShareSuccess) return Result<V>::err(rc);
+            std::vector<repr> coeffs(degree + 1);
+            for (size_t k = 0; k <= degree; ++k) coeffs[k] = rng().v;   // DensePolynomial::rand(degree, rng): degree + 1 draws (:73)
+            coeffs[0] = secret.v;                                       // :74
+            rc = FT::shamir_compute_shares(FT::context(), coeffs.data(), 1, points.data(), points.size(), degree, out.data());
+            if (rc != ShareSuccess) return Result<V>::err(rc);
+            V shares;
+            for (size_t i = 0; i < points.size(); ++i) shares.emplace_back(F(out[i]), (*ids)[i], degree);
+            return Result<V>::ok(std::move(shares));
+        }
+        // SecretSharingScheme::recover_secret (shamir.rs:90-125): `n` and `t` are unused there too
+        static Result<Recovered> recover_secret(const std::vector<ShamirShare<Shamir>>& shares, size_t /*n*/, size_t /*t*/) {
+            return recover_impl(shares, shares.size() + 1,
+                                [&](const size_t* ids, const size_t* degs, const repr* vals, repr* co, size_t* nco, repr* secret) {
+                                    const std::vector<uint64_t> points(ids, ids + shares.size());
+                                    return FT::shamir_recover_secret(FT::context(), points.data(), degs, vals, shares.size(), co, nco, secret);
+                                });
+        }
+    };
+
     // ---- make_vandermonde / apply_vandermonde (common/share/mod.rs:31-76) ---------------------------------
     using Matrix = std::vector<std::vector<F>>;
     static Result<Matrix> make_vandermonde(size_t n, size_t t) {
@@ -365,6 +406,7 @@ using ShamirShare = FrScheme::ShamirShare<P>;
 using Recovered = FrScheme::Recovered;
 using RobustShare = FrScheme::RobustShare;
 using NonRobustShare = FrScheme::NonRobustShare;
+using Shamirshare = FrScheme::Shamirshare;
 using Matrix = FrScheme::Matrix;
 inline Result<Matrix> make_vandermonde(size_t n, size_t t) { return FrScheme::make_vandermonde(n, t); }
 template <class P>

@@ -33,9 +33,12 @@ ShareErrorCode validate_senders(hbmpc_ctx* ctx, const size_t* sender_ids, size_t
     return ShareSuccess;
 }
 
+// pts: the ids are integer evaluation points (the Shamirshare scheme, capi_shamir.inc), not indices into the roots-of-unity domain:
+// a different table for the same numbers, so a different key
 std::string ids_key(const char* kind, const std::vector<size_t>& ids, size_t count, size_t n, size_t d, size_t t,
-                    int impl) {
-    std::string k = kind;
+                    int impl, bool pts = false) {
+    std::string k = pts ? "pt-" : "";
+    k += kind;
     k += ":" + std::to_string(n) + ":" + std::to_string(d) + ":" + std::to_string(t) + ":";
     for (size_t i = 0; i < count; ++i) k += std::to_string(ids[i]) + ",";
     return k + "#" + std::to_string(impl);
@@ -70,7 +73,7 @@ std::shared_ptr<const DomainInv<HGl>> domain_inv<HGl>(hbmpc_ctx* ctx, size_t n) 
 
 template <class H>
 std::vector<uint32_t> build_gao_tables_t(const DomainInv<H>& D, const std::vector<std::vector<size_t>>& known_sets, const std::vector<int>& ks,
-                                         const std::vector<size_t>& alpha_ids, int impl, GaoLayout* lay) {
+                                         const std::vector<size_t>& alpha_ids, int impl, GaoLayout* lay, bool alpha_points = false) {
     const int NL = impl_nl(impl);
     const std::vector<H>& el = D.el;
     H rdev = H::one();
@@ -115,7 +118,7 @@ std::vector<uint32_t> build_gao_tables_t(const DomainInv<H>& D, const std::vecto
         out.insert(out.end(), lbw[r].begin(), lbw[r].end());
     }
     lay->alpha_off = out.size();
-    for (size_t id : alpha_ids) put_const(out, el[id], impl);
+    for (size_t id : alpha_ids) put_const(out, alpha_points ? H::from_u64(id) : el[id], impl);  // integer points: F::from(id)
     lay->one_off = out.size();
     put_plain(out, H::one(), impl);
     while ((int)(out.size() - lay->one_off) < NL) out.push_back(0);
@@ -168,12 +171,22 @@ struct RecoverCall {
     int only_coeff = 0, second_coeff = -1;
     size_t group = 0, group_stride = 0;  // group q's values q * group_stride elements further on in every sender row (RecoverArgs::group)
     bool honest_majority = false;        // n >= 2t + 1 is enough (validate_senders)
+    // the integer-point scheme (capi_shamir.inc): sender i sits at F::from(points[i]), not at a domain element.  The caller has made the
+    // scheme's checks (distinct non-zero field elements); t == 0, S == d + 1 <= 255, n == S, sender_ids unused
+    const uint64_t* points = nullptr;
 };
 
 // the decode's table of a sender set: the verify rows (vm), then the coefficient rows (bc)
 template <class H>
-ShareErrorCode rec_table(hbmpc_ctx* ctx, const DomainInv<H>& dom, const std::vector<size_t>& ids, size_t n, size_t d, size_t t, const uint32_t** out) {
-    return get_table(ctx, ids_key("rec", ids, d + t + 1, n, d, t, ctx->impl), [&] {
+ShareErrorCode rec_table(hbmpc_ctx* ctx, const DomainInv<H>& dom, const std::vector<size_t>& ids, size_t n, size_t d, size_t t, const uint32_t** out,
+                         bool pts = false) {
+    return get_table(ctx, ids_key("rec", ids, d + t + 1, n, d, t, ctx->impl, pts), [&] {
+        if (pts) {  // no verify row: the S x S coefficient rows
+            std::vector<uint32_t> bc;
+            for (const auto& row : point_coeff_rows<H>(ids))
+                for (const H& v : row) put_const(bc, v, ctx->impl);
+            return bc;
+        }
         const RecoverTables T = build_recover_tables<H>(dom, ids, d, t, ctx->impl);
         std::vector<uint32_t> both = T.vm;
         both.insert(both.end(), T.bc.begin(), T.bc.end());
@@ -198,10 +211,10 @@ bool run_mfma_recover(hbmpc_ctx* ctx, const RecoverRoute& r, const SortedSenders
     // followed by coefficient row k
     const bool sel = c.only_coeff > 0 || c.second_coeff >= 0;
     const std::string tkey = ids_key(sel ? ("mfrec_k" + std::to_string(c.only_coeff) + "_" + std::to_string(c.second_coeff)).c_str() : "mfrec", ss.ids,
-                                     needed, n, d, t, ctx->impl);
+                                     needed, n, d, t, ctx->impl, c.points != nullptr);
     const auto dom = domain_inv<HFr>(ctx, n);  // before the table calls: their builders run under the context's lock, which this takes too
     auto table_rows = [&] {
-        std::vector<std::vector<HFr>> rows_all = recover_coeff_rows<HFr>(*dom, ss.ids, d, t);
+        std::vector<std::vector<HFr>> rows_all = c.points ? point_coeff_rows<HFr>(ss.ids) : recover_coeff_rows<HFr>(*dom, ss.ids, d, t);
         if (sel) {
             std::vector<std::vector<HFr>> picked(rows_all.begin(), rows_all.begin() + nv);
             picked.push_back(rows_all[nv + c.only_coeff]);
@@ -265,8 +278,8 @@ bool run_mfma_recover_gl(hbmpc_ctx* ctx, const RecoverRoute& r, const SortedSend
     const size_t n = c.n, d = c.d, t = c.t, m = d + 1, needed = d + t + 1, nv = needed - m, ow = c.p0 ? 1 : m;
     const auto domain_inv_gl = domain_inv<HGl>(ctx, n);
     const uint32_t* tab;
-    *rc_out = get_table(ctx, ids_key("mfrecgl", ss.ids, needed, n, d, t, ctx->impl), [&] {
-        return build_mfma_table_gl(recover_coeff_rows<HGl>(*domain_inv_gl, ss.ids, d, t), m);
+    *rc_out = get_table(ctx, ids_key("mfrecgl", ss.ids, needed, n, d, t, ctx->impl, c.points != nullptr), [&] {
+        return build_mfma_table_gl(c.points ? point_coeff_rows<HGl>(ss.ids) : recover_coeff_rows<HGl>(*domain_inv_gl, ss.ids, d, t), m);
     }, &tab);
     if (*rc_out != ShareSuccess) return true;
     mf::MfmaGlArgs a;
@@ -305,14 +318,23 @@ ShareErrorCode batch_recover_dev(hbmpc_ctx* ctx, RecoverCall c) {
     const size_t S = c.S, G = c.G, n = c.n, d = c.d, t = c.t;
     if (ctx && c.row_stride < (c.group ? c.group : G)) return fail(ctx, InvalidInput, "row_stride must be >= G");
     if (!ctx) return InvalidInput;
-    if (S && !c.sender_ids) return fail(ctx, InvalidInput, "null sender_ids");
+    const bool pts = c.points != nullptr;
+    if (S && !c.sender_ids && !pts) return fail(ctx, InvalidInput, "null sender_ids");
     const RecoverKnobs k = recover_knobs(ctx);
     RecoverShape sh{G, n, d, t, S};
     sh.p0 = c.p0, sh.only_coeff = c.only_coeff, sh.second_coeff = c.second_coeff, sh.group = c.group;
     sh.slots = c.slots != nullptr, sh.pair = c.pair != nullptr, sh.pair_N = c.pair ? c.pair->N : 0, sh.host_call = c.host_call;
     if (recover_cover(k, sh, true) != RecoverCover::Run) return HBMPC_NOT_FUSED;
     SortedSenders ss;
-    ShareErrorCode rc = validate_senders(ctx, c.sender_ids, S, G, n, d, c.second_coeff >= 0 ? 0 : t, &ss, c.honest_majority);
+    ShareErrorCode rc = ShareSuccess;
+    if (pts) {  // the points in the caller's order: row i is point i
+        if (G == 0 || t != 0 || S != d + 1 || n != S) return fail(ctx, InvalidInput, "integer points: the plain interpolation only");
+        ss.ids.assign(c.points, c.points + S);
+        ss.rows.resize(S);
+        for (size_t i = 0; i < S; ++i) ss.rows[i] = (int)i;
+    } else {
+        rc = validate_senders(ctx, c.sender_ids, S, G, n, d, c.second_coeff >= 0 ? 0 : t, &ss, c.honest_majority);
+    }
     if (rc != ShareSuccess) return rc;
     if (n > 255) return fail(ctx, InvalidInput, "n > 255 (HoneyBadgerMPCNodeOpts limits n to 255)");
     if (c.slots)
@@ -333,7 +355,7 @@ ShareErrorCode batch_recover_dev(hbmpc_ctx* ctx, RecoverCall c) {
     const std::shared_ptr<const DomainInv<HFr>> dom_fr = impl == IMPL_GOLD ? nullptr : domain_inv<HFr>(ctx, n);
     const std::shared_ptr<const DomainInv<HGl>> dom_gl = impl == IMPL_GOLD ? domain_inv<HGl>(ctx, n) : nullptr;
     const uint32_t* vm_bc;
-    rc = impl == IMPL_GOLD ? rec_table(ctx, *dom_gl, ss.ids, n, d, t, &vm_bc) : rec_table(ctx, *dom_fr, ss.ids, n, d, t, &vm_bc);
+    rc = impl == IMPL_GOLD ? rec_table(ctx, *dom_gl, ss.ids, n, d, t, &vm_bc, pts) : rec_table(ctx, *dom_fr, ss.ids, n, d, t, &vm_bc, pts);
     if (rc != ShareSuccess) return rc;
     const size_t vm_words = (needed - m) * m * impl_nl(impl);
     const uint32_t* sel2 = nullptr;  // second_coeff >= 0: [verify rows | row only_coeff | row second_coeff], contiguous
@@ -348,7 +370,7 @@ ShareErrorCode batch_recover_dev(hbmpc_ctx* ctx, RecoverCall c) {
         }, &sel2);
         if (rc != ShareSuccess) return rc;
     }
-    const std::string gao_key = ids_key("gao", ss.ids, S, n, d, t, impl), sc_key = ids_key("sc", ss.ids, S, n, d, t, impl);
+    const std::string gao_key = ids_key("gao", ss.ids, S, n, d, t, impl, pts), sc_key = ids_key("sc", ss.ids, S, n, d, t, impl, pts);
     RecoverFacts facts;
     facts.capturing = g_capturing > 0;
     // (only a call with OEC rounds has fallback tables: the others skip the look-ups)
@@ -369,8 +391,8 @@ ShareErrorCode batch_recover_dev(hbmpc_ctx* ctx, RecoverCall c) {
         std::array<size_t, 5> aux = {0, 0, 0, 0, 0};
         ShareErrorCode frc = get_table(ctx, gao_key, [&] {
             GaoLayout built;
-            std::vector<uint32_t> host = impl == IMPL_GOLD ? build_gao_tables_t<HGl>(*dom_gl, known_sets, ks, ss.ids, impl, &built)
-                                                           : build_gao_tables_t<HFr>(*dom_fr, known_sets, ks, ss.ids, impl, &built);
+            std::vector<uint32_t> host = impl == IMPL_GOLD ? build_gao_tables_t<HGl>(*dom_gl, known_sets, ks, ss.ids, impl, &built, pts)
+                                                           : build_gao_tables_t<HFr>(*dom_fr, known_sets, ks, ss.ids, impl, &built, pts);
             aux = {(size_t)built.n_rounds, built.alpha_off, built.one_off, built.r2_off, built.exp_off};
             return host;
         }, &gao_dev, &aux);
@@ -683,14 +705,16 @@ TYPED_RECOVER(uint64_t, REQ_GL, hbmpc_gl_)
 // coeffs_out_dev is then a [G][S] workspace that the fused kernel does not touch
 static ShareErrorCode batch_interpolate_dev(hbmpc_ctx* ctx, const size_t* ids, size_t S, const void* evals_dev,
                                             size_t row_stride, size_t G, size_t n, void* coeffs_out_dev,
-                                            uint32_t* degree_out_dev, void* stream, void* c0_out_dev = nullptr) {
+                                            uint32_t* degree_out_dev, void* stream, void* c0_out_dev = nullptr,
+                                            const uint64_t* points = nullptr) {
+    // points: the integer-point scheme (capi_shamir.inc, which has checked them): ids unused, n == S, no inverse DFT
     if (!ctx) return InvalidInput;
     if (S == 0 || G == 0) return fail(ctx, InvalidInput, "empty input");            // shamir.rs:204
-    if (!ids || !evals_dev || !coeffs_out_dev) return fail(ctx, InvalidInput, "null buffer");
+    if ((!ids && !points) || !evals_dev || !coeffs_out_dev) return fail(ctx, InvalidInput, "null buffer");
     ShareErrorCode rc = ShareSuccess;
     bool done = false, degree_in_kernel = false;
     const InterpPlan plan = plan_interpolate(recover_knobs(ctx), G, n, S, row_stride, degree_out_dev != nullptr, c0_out_dev != nullptr);
-    if (plan.route[0] != InterpKernel::Decode) {  // the inverse DFT on point pairs (recover_route.hpp)
+    if (!points && plan.route[0] != InterpKernel::Decode) {  // the inverse DFT on point pairs (recover_route.hpp)
         SortedSenders ss;
         rc = validate_senders(ctx, ids, S, G, n, S - 1, 0, &ss);
         if (rc != ShareSuccess) return rc;
@@ -733,7 +757,7 @@ static ShareErrorCode batch_interpolate_dev(hbmpc_ctx* ctx, const size_t* ids, s
     }
     if (!done)
         rc = batch_recover_dev(ctx, {.sender_ids = ids, .S = S, .evals = evals_dev, .row_stride = row_stride, .G = G, .n = n, .d = S - 1, .t = 0,
-                                     .out = coeffs_out_dev, .stream = stream});
+                                     .out = coeffs_out_dev, .stream = stream, .points = points});
     if (rc != ShareSuccess) return rc;
     if (degree_out_dev && !degree_in_kernel) {  // one pass for the degree and, where asked for, the constant term
         launch_poly_degree((const uint64_t*)coeffs_out_dev, G, (int)S, (int)(ebytes(ctx) / 8), degree_out_dev, pick(ctx, stream), (uint64_t*)c0_out_dev);

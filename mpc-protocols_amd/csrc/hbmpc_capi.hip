@@ -40,6 +40,7 @@
 #include "producer_route.hpp"
 #include "prandbit_route.hpp"
 #include "take_plan.hpp"
+#include "shamir_route.hpp"
 #include "tables_sqrt.hpp"
 #include "tables_riss.hpp"
 
@@ -120,6 +121,7 @@ struct hbmpc_ctx {
     int n_cus = 256;
     int riss_form = 0;                             // RISS conversion (kernels_riss.hpp): 0 = by size, 1 = always 16 parties per workgroup, 2 = always one (A/B aid)
     int mfma_wgs = 0;                              // test aid: workgroups of a matrix-core launch (0 = one per CU)
+    int shamir_route = 0;                          // test and sweep aid: the integer-point encode's forced route (shamir_route.hpp: SHAMIR_ROUTE_*)
     std::map<hipStream_t, Scratch> scratch;        // per-stream scratch (calls on one stream are ordered)
     std::vector<std::pair<void*, size_t>> stage_free;  // device staging buffers of the host-pointer API, kept between calls
     size_t stage_bytes = 0;
@@ -2371,3 +2373,4 @@ extern "C" ShareErrorCode hbmpc_dev_fpmul_parties(hbmpc_ctx* ctx, const size_t* 
 #include "capi_prandbit.inc"
 #include "capi_riss_seeded.inc"
 #include "capi_producers.inc"
+#include "capi_shamir.inc"

@@ -69,6 +69,10 @@ bool launch_gold_fft1(int log, int cnt, const uint32_t* x, size_t G, int n, cons
 bool launch_gold_fftP(int dp1, const uint32_t* x, size_t G, int n, int P, const uint32_t* tw16, const uint32_t* twist,
                       EvalOut y, hipStream_t s);
 bool launch_gold_recover(int m, bool p0, const RecoverArgs& ra, unsigned grid, hipStream_t s);
+// the small-weight encode of the integer-point Shamir scheme (kernels_shamir.hpp); nl = 8 (Fr) or 2 (Goldilocks), the launch shape from
+// plan_shamir_encode (shamir_route.hpp)
+void launch_shamir_encode(int nl, bool w32, const void* coeffs, size_t B, int m, int dp1, const uint64_t* w, void* out, int waves,
+                          size_t lds_bytes, int row_units, hipStream_t s);
 // generic Horner evaluation
 void launch_eval_generic(int impl, const uint32_t* x, size_t G, int n, int dp1, const uint32_t* alpha, EvalOut y,
                          hipStream_t s);

@@ -274,6 +274,20 @@ template <class H>
 inline std::vector<std::vector<H>> recover_coeff_rows(const std::vector<size_t>& sorted_ids, size_t n, size_t d, size_t t) {
     return recover_coeff_rows<H>(DomainInv<H>(n), sorted_ids, d, t);
 }
+// the coefficient rows of the interpolation through arbitrary distinct points (the layout of recover_coeff_rows with no verify row) -- the integer-point
+// Shamir scheme, point i = F::from(points[i]):
+// row k = (coefficient k of L_i)_i
+template <class H>
+inline std::vector<std::vector<H>> point_coeff_rows(const std::vector<size_t>& points) {
+    std::vector<H> xs(points.size());
+    for (size_t i = 0; i < points.size(); ++i) xs[i] = H::from_u64(points[i]);
+    const auto basis = lagrange_basis(xs);
+    std::vector<std::vector<H>> rows(xs.size(), std::vector<H>(xs.size()));
+    for (size_t k = 0; k < xs.size(); ++k)
+        for (size_t i = 0; i < xs.size(); ++i) rows[k][i] = basis[i][k];
+    return rows;
+}
+
 template <class H = HFr>
 inline RecoverTables build_recover_tables(const DomainInv<H>& D, const std::vector<size_t>& sorted_ids, size_t d, size_t t, int impl) {
     const size_t m = d + 1, needed = d + t + 1;

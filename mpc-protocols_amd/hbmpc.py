@@ -294,6 +294,64 @@ class Engine:
                                             C.c_size_t(n), _p(co), _p(deg))
         return rc, co, deg
 
+    # ---- Shamirshare: the integer-point scheme (common/share/shamir.rs:13-126); points are u64 ids, NOT domain indices ----
+    @staticmethod
+    def _pts(points):
+        return None if points is None else _sz([int(x) for x in points])
+
+    def shamir_compute_shares(self, coeffs, points, d):
+        """coeffs [B][d+1] -> (rc, shares [m][B]), shares[i][b] = sum_k coeffs[b][k] points[i]^k"""
+        coeffs = np.ascontiguousarray(coeffs)
+        B, m = coeffs.shape[0], (0 if points is None else len(points))
+        out = self._new((m, B))
+        rc = self._f("shamir_compute_shares")(self.ctx, _p(coeffs), C.c_size_t(B), _p(self._pts(points)), C.c_size_t(m), C.c_size_t(d), _p(out))
+        return rc, out
+
+    def shamir_recover_secret(self, ids, degrees, vals):
+        """(rc, trimmed coefficients, secret) of one polynomial: shamir.rs:90-125"""
+        vals = np.ascontiguousarray(vals)
+        S = len(ids)
+        out = self._new((max(S, 1),))
+        nco = C.c_size_t(0)
+        sec = self._new((1,))
+        rc = self._f("shamir_recover_secret")(self.ctx, _p(self._pts(ids)), _p(_sz(degrees)), _p(vals), C.c_size_t(S), _p(out), C.byref(nco),
+                                              _p(sec))
+        return rc, out[: nco.value], sec[0]
+
+    def shamir_batch_interpolate(self, points, evals):
+        """evals [S][G] -> (rc, coeffs [G][S] untrimmed, degree [G]): plain Lagrange through all S points"""
+        evals = np.ascontiguousarray(evals)
+        S, G = len(points), evals.shape[1]
+        co = self._new((G, S))
+        deg = np.zeros(G, dtype=np.uint32)
+        rc = self._f("shamir_batch_interpolate")(self.ctx, _p(self._pts(points)), C.c_size_t(S), _p(evals), C.c_size_t(G), _p(co), _p(deg))
+        return rc, co, deg
+
+    def dev_shamir_compute_shares(self, coeffs_d, B, points, d, out_d, stream=0):
+        m = 0 if points is None else len(points)
+        return self._f("dev_shamir_compute_shares")(self.ctx, C.c_void_p(coeffs_d), C.c_size_t(B), _p(self._pts(points)), C.c_size_t(m),
+                                                    C.c_size_t(d), C.c_void_p(out_d), C.c_void_p(stream))
+
+    def dev_shamir_batch_interpolate(self, points, evals_d, row_stride, G, coeffs_d, degree_d, stream=0):
+        return self._f("dev_shamir_batch_interpolate")(self.ctx, _p(self._pts(points)), C.c_size_t(len(points)), C.c_void_p(evals_d),
+                                                       C.c_size_t(row_stride), C.c_size_t(G), C.c_void_p(coeffs_d), C.c_void_p(degree_d),
+                                                       C.c_void_p(stream))
+
+    def dev_shamir_batch_interpolate_c0(self, points, evals_d, row_stride, G, tmp_coeffs_d, c0_d, degree_d, stream=0):
+        return self._f("dev_shamir_batch_interpolate_c0")(self.ctx, _p(self._pts(points)), C.c_size_t(len(points)), C.c_void_p(evals_d),
+                                                          C.c_size_t(row_stride), C.c_size_t(G), C.c_void_p(tmp_coeffs_d), C.c_void_p(c0_d),
+                                                          C.c_void_p(degree_d), C.c_void_p(stream))
+
+    def set_shamir_route(self, route: int):
+        """0 = the planner's rule (csrc/shamir_route.hpp), 1 = the small-weight kernel wherever it covers the call, 2 = never"""
+        assert self.L.hbmpc_set_shamir_route(self.ctx, C.c_int(route)) == 0
+
+    def shamir_route(self, points, d, B):
+        """(rc, kernel): the kernel the planner picks for the call (1 small-weight, 2 a wave per secret, 3 a lane per secret)"""
+        k = C.c_int(0)
+        rc = self.L.hbmpc_shamir_route(self.ctx, _p(self._pts(points)), C.c_size_t(len(points)), C.c_size_t(d), C.c_size_t(B), C.byref(k))
+        return rc, k.value
+
     def _ew(self, name, ins, n_out=1, extra=()):
         ins = [np.ascontiguousarray(a) for a in ins]
         N = ins[0].shape[0]

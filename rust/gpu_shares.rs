@@ -715,3 +715,79 @@ impl SecretSharingScheme<Fr> for GpuRobustShare {
         global().lock().expect("hbmpc context poisoned").recover_secret(&inner, n, t)
     }
 }
+
+/// `Shamirshare<Fr>` (common/share/shamir.rs:13-126: shares at the field elements `Fr::from(id as u64)`, recovery by plain
+/// Lagrange) whose scheme functions run on the GPU.  The share record is the reference's own.
+#[derive(Clone, Debug)]
+pub struct GpuShamirshare(pub crate::common::share::shamir::Shamirshare<Fr>);
+
+/// `ShareErrorCode` -> `ShareError`, the error type of `Shamirshare` (shamir.rs:42)
+fn share_error(rc: sys::ShareErrorCode) -> Result<(), ShareError> {
+    match rc {
+        sys::ShareSuccess => Ok(()),
+        sys::InsufficientShares => Err(ShareError::InsufficientShares),
+        sys::DegreeMismatch => Err(ShareError::DegreeMismatch),
+        sys::IdMismatch => Err(ShareError::IdMismatch),
+        sys::TypeMismatch => Err(ShareError::TypeMismatch),
+        _ => Err(ShareError::InvalidInput), // InvalidInput and the library's own codes (no device, out of memory)
+    }
+}
+
+impl GpuShares {
+    /// `B` calls of `Shamirshare::compute_shares` (shamir.rs:44-88) in one launch, the rng drawn as the reference draws it per
+    /// secret.  Returns `[id i][secret b]`.  The checks, in the reference's order, are the library's (include/hbmpc_hip.h).
+    pub fn shamir_compute_shares_batch(&self, secrets: &[Fr], degree: usize, ids: Option<&[usize]>, rng: &mut impl Rng)
+        -> Result<Vec<Vec<crate::common::share::shamir::Shamirshare<Fr>>>, ShareError> {
+        use crate::common::share::shamir::Shamirshare;
+        let b = secrets.len();
+        let points: Option<Vec<u64>> = ids.map(|l| l.iter().map(|&i| i as u64).collect());
+        let (pp, m) = points.as_ref().map_or((std::ptr::null(), 0), |p| (p.as_ptr(), p.len()));
+        // the id checks come before DensePolynomial::rand in the reference: a refused call consumes no draw (B = 0 checks only)
+        share_error(unsafe { sys::hbmpc_shamir_compute_shares(self.ctx, std::ptr::null(), 0, pp, m, degree, std::ptr::null_mut()) })?;
+        let mut coeffs = Vec::<sys::U256>::with_capacity(b * (degree + 1));
+        for s in secrets {
+            let mut poly = DensePolynomial::<Fr>::rand(degree, rng); // (:73)
+            poly.coeffs[0] = *s; // (:74)
+            coeffs.extend(poly.coeffs.iter().map(to_u256));
+        }
+        let mut out = vec![sys::U256::default(); m * b];
+        share_error(unsafe { sys::hbmpc_shamir_compute_shares(self.ctx, coeffs.as_ptr(), b, pp, m, degree, out.as_mut_ptr()) })?;
+        let ids = ids.unwrap_or(&[]);
+        Ok((0..m)
+            .map(|i| out[i * b..(i + 1) * b].iter().map(|v| Shamirshare::new(from_u256(v), ids[i], degree)).collect())
+            .collect())
+    }
+
+    /// `Shamirshare::recover_secret` (shamir.rs:90-125), the checks in its order
+    pub fn shamir_recover_secret(&self, shares: &[crate::common::share::shamir::Shamirshare<Fr>]) -> Result<(Vec<Fr>, Fr), ShareError> {
+        let s = shares.len();
+        let ids: Vec<u64> = shares.iter().map(|x| x.id as u64).collect();
+        let degrees: Vec<usize> = shares.iter().map(|x| x.degree).collect();
+        let vals: Vec<sys::U256> = shares.iter().map(|x| to_u256(&x.share[0])).collect();
+        let mut coeffs = vec![sys::U256::default(); s.max(1)];
+        let mut ncoeffs: usize = 0;
+        let mut secret = sys::U256::default();
+        share_error(unsafe {
+            sys::hbmpc_shamir_recover_secret(self.ctx, ids.as_ptr(), degrees.as_ptr(), vals.as_ptr(), s, coeffs.as_mut_ptr(), &mut ncoeffs,
+                                             &mut secret)
+        })?;
+        Ok((coeffs[..ncoeffs].iter().map(from_u256).collect(), from_u256(&secret)))
+    }
+}
+
+impl SecretSharingScheme<Fr> for GpuShamirshare {
+    type SecretType = Fr;
+    type Error = ShareError;
+
+    /// one secret = a batch of one; `_n` is unused, as in the reference (shamir.rs:46)
+    fn compute_shares(secret: Fr, _n: usize, degree: usize, ids: Option<&[usize]>, rng: &mut impl Rng) -> Result<Vec<Self>, ShareError> {
+        let gpu = global().lock().expect("hbmpc context poisoned");
+        let by_id = gpu.shamir_compute_shares_batch(&[secret], degree, ids, rng)?;
+        Ok(by_id.into_iter().map(|mut row| GpuShamirshare(row.remove(0))).collect())
+    }
+
+    fn recover_secret(shares: &[Self], _n: usize, _t: usize) -> Result<(Vec<Fr>, Fr), ShareError> {
+        let inner: Vec<_> = shares.iter().map(|s| s.0.clone()).collect();
+        global().lock().expect("hbmpc context poisoned").shamir_recover_secret(&inner)
+    }
+}
